@@ -29,8 +29,17 @@ rotates the sponge.  The warm-up frames walk up to the start pose, the timed
 frames walk on from it (deterministic poses; their ray-steps are counted by an
 instrumented pass over the same poses before timing).
 
-Usage: python bench.py [--gpus N --steps K --warmup W] [--scene T|O|S0]
-       [--size 4096] [--max-steps 256] [--pose P0] [--band 16] [--walk]
+A plain run does what the headline figure needs and no more: it sets up,
+counts the frame's ray-steps, warms up, times the K steps and prints the result
+line.  --full adds everything else the line can report, each from runs of its
+own after the timed region: the render kernel's per-launch duration and its
+roofline, the frame check against the instrumented kernel, for N > 1 the
+exchange's steps timed one by one, the post passes and the whole pipeline, and
+the CPU baseline.  --dump-outputs DIR writes the last timed frame (rank 0's) as
+DIR/frame.npy for comparing two builds output for output.
+
+Usage: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
+       [--scene T|O|S0] [--size 4096] [--max-steps 256] [--pose P0] [--band 16] [--walk]
        [--fmt rgba8|float4] [--kernel auto|tile16|tile8] [--cpu-seconds 12]
 Multi-GPU: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N
 """
@@ -55,6 +64,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need, in runs of their own "
+                         "after the timed steps: kernel_ms and the roofline, frame_check, the exchange's steps "
+                         "(N > 1), the post passes, the pipeline and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed frame (what rank 0 holds after the last step) to DIR/frame.npy "
+                         "as float32 channel values, a fixed seeded sample of its pixels when the frame is larger "
+                         "than DUMP_MAX_BYTES (then DIR/frame_pixels.npy holds the sampled pixel indices)")
     ap.add_argument("--spinup", type=float, default=0.3,
                     help="seconds of untimed frames before the warm-up frames (GPU clock ramp)")
     ap.add_argument("--scene", default="T")
@@ -91,7 +108,7 @@ def parse():
                     help="moving camera and advancing u_time (main.cpp's W key at 60 Hz) instead of a still pose")
     ap.add_argument("--walk-speed", type=float, default=0.1, help="camera step per frame (main.cpp:21 speed)")
     ap.add_argument("--walk-dt", type=float, default=1.0 / 60.0, help="u_time step per frame (main.cpp:30)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU-baseline budget (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: CPU-baseline budget (0 = skip)")
     ap.add_argument("--post-pmc", default=os.path.join(HERE, "profiles", "pmc_post.json"),
                     help="per post pass rocprofv3 HBM bytes (tools/make_post_traffic.py)")
     ap.add_argument("--pmc", default=os.path.join(HERE, "profiles", "pmc_counters.json"),
@@ -201,6 +218,31 @@ def frame_check(r, frame, W, H, fmt):
         print(json.dumps({"frame_check": res}), file=sys.stderr, flush=True)
         raise SystemExit(f"frame_check: {nd} of {W * H} pixels of the timed frame differ from the instrumented frame")
     return res
+
+
+DUMP_MAX_BYTES = 32 << 20  # of frame.npy; with frame_pixels.npy (float64 indices) at most 48 MiB in all
+DUMP_SEED = 20240607
+
+
+def dump_outputs(path, frame, fmt):
+    """Write the frame the timed path left on rank 0 after its last step --
+    the (H, W) RGBA8 words or the (H, W, 4) float frame a caller of
+    DistributedFrame.submit()/flush() receives -- as path/frame.npy: float32,
+    one row of 4 channel values per pixel (RGBA8 bytes as 0..255).  A frame
+    larger than DUMP_MAX_BYTES is sampled: the same DUMP_SEED-drawn pixels every
+    run, in ascending order, their flat indices (y * W + x) beside the values
+    in path/frame_pixels.npy (float64, exact below 2^53)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    px = frame.view(torch.uint8).reshape(-1, 4) if fmt == "rgba8" else frame.reshape(-1, 4)
+    n, keep = px.shape[0], DUMP_MAX_BYTES // 16
+    if n > keep:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=keep, replace=False))
+        px = px[torch.from_numpy(idx).to(px.device)]
+        np.save(os.path.join(path, "frame_pixels.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, "frame.npy"), px.to(torch.float32).cpu().numpy())
 
 
 def _median(xs):
@@ -516,6 +558,36 @@ def roofline(pmc, kern_ms, executed_steps, out_bytes, flop_tally, evals, exact=T
     return roof
 
 
+def launch_roofline(args, W, H, world, rank_launch, ms_step, flop_rank, evals_rank, code_hash):
+    """--full: the result line's roofline from every rank's launch
+    (rank_launch: kernel_ms, executed_steps, rows per rank), priced by the PMC
+    counters of this workload in args.pmc."""
+    pmc = {}
+    try:
+        pm = json.load(open(args.pmc))
+        # counters of one N = 1 launch of this frame at this pose (a rank's
+        # share, or a walk's other poses, are priced per executed ray-step)
+        pmc = pm.get(f"{args.scene}_{W}x{H}_{args.max_steps}_{args.pose}", {})
+    except (OSError, ValueError):
+        pass
+    exact = world == 1 and not args.walk
+    # the roofline's launch: the slowest rank's (kernel_ms_max_rank), priced
+    # by its own executed ray-steps; every rank's beside it
+    crit = max(range(len(rank_launch)), key=lambda q: rank_launch[q]["kernel_ms"])
+    cl = rank_launch[crit]
+    # the roofline's launch duration: the median synchronous launch, never longer than the driver-timed step
+    roof = roofline(pmc, min(cl["kernel_ms"], ms_step), cl["executed_steps"],
+                    W * cl["rows"] * (4 if args.fmt == "rgba8" else 16), flop_rank if crit == 0 else None,
+                    evals_rank if crit == 0 else None, exact=exact, rows_frac=cl["rows"] / H, code_hash=code_hash)
+    roof["render_code_hash"] = code_hash
+    if world > 1:
+        roof["rank"] = crit
+        roof["per_rank_frac"] = [roofline(pmc, q["kernel_ms"], q["executed_steps"], 0, None, None, exact=False,
+                                          rows_frac=q["rows"] / H, code_hash=code_hash)["frac"]
+                                 for q in rank_launch]
+    return roof
+
+
 def main():
     args = parse()
     import torch
@@ -728,17 +800,20 @@ def main():
         frame_stream_ms = evs[0][0][0].elapsed_time(evs[0][0][1]) / args.steps if live else 0.0
     else:
         frame_stream_ms = sum(evs[i][c][0].elapsed_time(evs[i][c][1]) for i in range(args.steps) for c in live) / args.steps
-    # per-launch render-kernel duration (the roofline denominator): synchronous launches of this rank's
-    # rows on the frames' stream, HIP events around the kernel alone (rm_stats.kernel_ms), after the
-    # timed region
-    set_frame(args.steps - 1)
-    launch = sorted(fr.render_local(stats=True)[1]["kernel_ms"] for _ in range(11)) if fr.nmine else [0.0]
-    kern = launch[len(launch) // 2]
-    kt = torch.tensor([kern], dtype=torch.float64, device=red_dev)
-    # the last timed frame against the instrumented kernel's frame of the same pose (rank 0)
-    check = frame_check(r, last_frame, W, H, args.fmt) if rank == 0 else None
-    exchange = None
-    if world > 1:
+    if args.dump_outputs and last_frame is not None:
+        dump_outputs(args.dump_outputs, last_frame, args.fmt)
+    kern, kt, check, exchange = None, None, None, None
+    if args.full:
+        # per-launch render-kernel duration (the roofline denominator): synchronous launches of this rank's
+        # rows on the frames' stream, HIP events around the kernel alone (rm_stats.kernel_ms), after the
+        # timed region
+        set_frame(args.steps - 1)
+        launch = sorted(fr.render_local(stats=True)[1]["kernel_ms"] for _ in range(11)) if fr.nmine else [0.0]
+        kern = launch[len(launch) // 2]
+        kt = torch.tensor([kern], dtype=torch.float64, device=red_dev)
+        # the last timed frame against the instrumented kernel's frame of the same pose (rank 0)
+        check = frame_check(r, last_frame, W, H, args.fmt) if rank == 0 else None
+    if world > 1 and args.full:
         # the frame's steps one at a time (render, pack, gather, de-interleave),
         # each timed alone after the timed region: the gather's own time, which
         # the pipelined frames overlap with the next frame's render
@@ -770,38 +845,18 @@ def main():
                     "deinterleave = rank 0's de-interleave kernel; the timed frames pipeline frame k's gather "
                     "and de-interleave with frame k+1's render",
         }
+    if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dist.all_reduce(kt, op=dist.ReduceOp.MAX)
-    elapsed, kern_max = float(t.item()), float(kt.item())
+        if args.full:
+            dist.all_reduce(kt, op=dist.ReduceOp.MAX)
+    elapsed, kern_max = float(t.item()), float(kt.item()) if args.full else None
 
     if rank == 0:
-        flop_rank = st["flop"]
-        pmc = {}
-        try:
-            pm = json.load(open(args.pmc))
-            # counters of one N = 1 launch of this frame at this pose (a rank's
-            # share, or a walk's other poses, are priced per executed ray-step)
-            pmc = pm.get(f"{args.scene}_{W}x{H}_{args.max_steps}_{args.pose}", {})
-        except (OSError, ValueError):
-            pass
-        exact = world == 1 and not args.walk
-        rank_launch[0]["kernel_ms"] = kern
-        # the roofline's launch: the slowest rank's (kernel_ms_max_rank), priced
-        # by its own executed ray-steps; every rank's beside it
-        crit = max(range(len(rank_launch)), key=lambda q: rank_launch[q]["kernel_ms"])
-        cl = rank_launch[crit]
-        ms_step = elapsed / args.steps * 1e3
-        # the roofline's launch duration: the median synchronous launch, never longer than the driver-timed step
-        code_hash = rm.render_code_hash()
-        roof = roofline(pmc, min(cl["kernel_ms"], ms_step), cl["executed_steps"],
-                        W * cl["rows"] * (4 if args.fmt == "rgba8" else 16), flop_rank if crit == 0 else None,
-                        evals_rank if crit == 0 else None, exact=exact, rows_frac=cl["rows"] / H, code_hash=code_hash)
-        roof["render_code_hash"] = code_hash
-        if world > 1:
-            roof["rank"] = crit
-            roof["per_rank_frac"] = [roofline(pmc, q["kernel_ms"], q["executed_steps"], 0, None, None, exact=False,
-                                              rows_frac=q["rows"] / H, code_hash=code_hash)["frac"]
-                                     for q in rank_launch]
+        roof = None
+        if args.full:
+            rank_launch[0]["kernel_ms"] = kern
+            roof = launch_roofline(args, W, H, world, rank_launch, elapsed / args.steps * 1e3, st["flop"], evals_rank,
+                                   rm.render_code_hash())
         res = {
             "metric": "ray-steps/sec + frames/sec at 4096\u00d74096, 1/2/4/8 MI355X",
             "value": evals_frame * args.steps / elapsed,
@@ -841,27 +896,33 @@ def main():
                           "T's reflection march past depth 3; DESIGN.md 2.11-2.13), so they execute "
                           "executed_ray_steps_per_s; frames_per_s is the same either way",
             "executed_ray_steps_per_s": (evals_frame - skipped_frame) * args.steps / elapsed,
-            "kernel_ms": kern, "kernel_ms_max_rank": kern_max, "frame_stream_ms": frame_stream_ms,
-            "kernel_ms_note": "median per-launch duration of the render kernel (HIP events on its stream, "
-                              "synchronous launches after the timed region, adaptive dispatch order as in the "
-                              "timed frames); frame_stream_ms = mean interval of the timed frames' render calls "
-                              "(kernel + dispatch-order sort; with 2 streams it spans overlapping frames)",
-            "roofline": roof,
-            "frame_check": check,
+            "frame_stream_ms": frame_stream_ms,
+            "frame_stream_ms_note": "mean interval of the timed frames' render calls (kernel + dispatch-order sort; "
+                                    "with 2 streams it spans overlapping frames)",
+            "full": args.full,
         }
         if balance is not None:
             res["balance"] = balance
-        if exchange is not None:
-            res.update(exchange)
-        if fr.frame is not None and fr.fmt == "rgba8":
-            counters = load_post_counters(args.post_pmc)
-            res["post_pass"] = time_fxaa(r, fr.frame, stream, counters)
-            res["bloom_pass"] = time_bloom(r, fr.frame, stream, counters)
-            if world == 1:
-                res["pipeline"] = time_pipeline(r, W, H, stream, counters, res["ms_per_step"])
-                res["pipeline_ms"] = res["pipeline"]["pipeline_ms"]
-        if world == 1 and args.cpu_seconds > 0:
-            res["cpu_baseline"] = cpu_baseline(args, pose, W, H, args.cpu_seconds)
+        if args.full:
+            res.update({
+                "kernel_ms": kern, "kernel_ms_max_rank": kern_max,
+                "kernel_ms_note": "median per-launch duration of the render kernel (HIP events on its stream, "
+                                  "synchronous launches after the timed region, adaptive dispatch order as in the "
+                                  "timed frames)",
+                "roofline": roof,
+                "frame_check": check,
+            })
+            if exchange is not None:
+                res.update(exchange)
+            if fr.frame is not None and fr.fmt == "rgba8":
+                counters = load_post_counters(args.post_pmc)
+                res["post_pass"] = time_fxaa(r, fr.frame, stream, counters)
+                res["bloom_pass"] = time_bloom(r, fr.frame, stream, counters)
+                if world == 1:
+                    res["pipeline"] = time_pipeline(r, W, H, stream, counters, res["ms_per_step"])
+                    res["pipeline_ms"] = res["pipeline"]["pipeline_ms"]
+            if world == 1 and args.cpu_seconds > 0:
+                res["cpu_baseline"] = cpu_baseline(args, pose, W, H, args.cpu_seconds)
         print(json.dumps(res), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -13,7 +13,8 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--steps", "3", "--warmup", "1", "--spinup", "0", "--size", "512", "--cpu-seconds", "0"]
+PLAIN = ["--steps", "3", "--warmup", "1", "--spinup", "0", "--size", "512"]
+SMALL = PLAIN + ["--full", "--cpu-seconds", "0"]  # --full: the checks and figures beside the headline one
 
 
 def _free_port():

@@ -17,14 +17,14 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { echo "smoke failed"; tail -20 $O/smoke.log; exit 3; }
   tail -1 $O/smoke.log
 fi
-timeout -k 10 300 python bench.py > $O/bench_C3.json 2> $O/bench_C3.err || { echo "bench C3 failed"; tail -20 $O/bench_C3.err; exit 4; }
+timeout -k 10 300 python bench.py --full > $O/bench_C3.json 2> $O/bench_C3.err || { echo "bench C3 failed"; tail -20 $O/bench_C3.err; exit 4; }
 python -c "import json,sys; d=json.load(open(sys.argv[1])); print('C3 ms/step', round(d['ms_per_step'],4), 'kernel', round(d['kernel_ms'],4), 'frac', d['roofline']['frac'], 'fxaa', round(d['post_pass']['ms'],4), 'bloom', round(d['bloom_pass']['ms'],4))" $O/bench_C3.json
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_C3 -o run -- python bench.py --cpu-seconds 0 > $O/bench_C3_under_rocprof.json 2> $O/bench_C3_under_rocprof.err || { echo "rocprof C3 failed"; exit 5; }
 find $O/trace_C3 -name "*kernel_stats.csv" -exec cp {} $O/bench_C3_kernel_stats.csv \;
 FRAME=random timeout -k 10 120 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_fxaa_random -o run -- python tools/post_probe.py fxaa 4096 4096 20 > $O/trace_fxaa_random.log 2>&1 || { echo "fxaa noise trace failed"; exit 5; }
-timeout -k 10 300 python bench.py --scene O --size 8192 --max-steps 512 --steps 5 --warmup 2 --cpu-seconds 0 > $O/bench_C5frame.json 2> $O/bench_C5frame.err || { echo "bench C5 failed"; tail -20 $O/bench_C5frame.err; exit 6; }
+timeout -k 10 300 python bench.py --scene O --size 8192 --max-steps 512 --steps 5 --warmup 2 --full --cpu-seconds 0 > $O/bench_C5frame.json 2> $O/bench_C5frame.err || { echo "bench C5 failed"; tail -20 $O/bench_C5frame.err; exit 6; }
 python -c "import json,sys; d=json.load(open(sys.argv[1])); print('C5 ms/step', round(d['ms_per_step'],4), 'kernel', round(d['kernel_ms'],4), 'frac', d['roofline']['frac'])" $O/bench_C5frame.json
-timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --backend gloo --cpu-seconds 0 > $O/bench_n2_gloo.json 2> $O/bench_n2_gloo.err || { echo "gloo N=2 failed"; tail -20 $O/bench_n2_gloo.err; exit 7; }
+timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --backend gloo --full --cpu-seconds 0 > $O/bench_n2_gloo.json 2> $O/bench_n2_gloo.err || { echo "gloo N=2 failed"; tail -20 $O/bench_n2_gloo.err; exit 7; }
 python -c "import json,sys; d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1]); r=d['roofline']; print('N2 gloo ms/step', round(d['ms_per_step'],4), 'frac', r['frac'], 'per_rank', r.get('per_rank_frac'), 'runs', d['balance']['runs'])" $O/bench_n2_gloo.json
 if [ "${PMC:-0}" = 1 ]; then
   bash tools/pmc_profile.sh T4096$TAG || exit 8

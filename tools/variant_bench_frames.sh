@@ -4,7 +4,7 @@ set -e
 out=$1; shift
 for rep in 1 2; do
   for lib in "$@"; do
-    RM_LIB=$lib timeout -k 10 120 python bench.py --steps 100 --cpu-seconds 0 $BENCH_ARGS > gpurun_out/vbf.json 2>/dev/null
-    python -c "import json,sys;d=json.load(open('gpurun_out/vbf.json'));print('$(basename $lib)',round(d['ms_per_step'],4),round(d['kernel_ms'],4),d['frame_check']['result'])" >> $out
+    RM_LIB=$lib timeout -k 10 120 python bench.py --full --steps 100 --cpu-seconds 0 $BENCH_ARGS > $out.last.json 2>/dev/null
+    python -c "import json,sys;d=json.load(open('$out.last.json'));print('$(basename $lib)',round(d['ms_per_step'],4),round(d['kernel_ms'],4),d['frame_check']['result'])" >> $out
   done
 done
