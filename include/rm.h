@@ -337,8 +337,14 @@ rm_status rm_deinterleave_cycle_rgb8(rm_ctx *ctx, int W, int H, int cycle, int n
  * (asynchronous, ctx stream).  rm_wire_decode: a message of nrows rows of the
  * cyclic part (cycle, offset, run) into those rows of the W x H RGBA8 frame.
  * rm_scatter_part_rgba8: a part's packed RGBA8 rows into their frame rows
- * (the root's own part).  Capacity/workspace return -1 for bad sizes
- * (W <= 2^18). */
+ * (the root's own part).
+ * One size rule for a part of nrows rows of W pixels, T = ceil(W / 8) *
+ * ceil(nrows / 8) tiles: 0 < W <= 2^18, 0 <= nrows <= 65535 and 25 T < 2^27
+ * (a tile is at most 25 words, and a table entry holds a tile's word offset in
+ * 27 bits; about 5.37 M tiles).  A part outside it is refused by every call of
+ * this section and by rm_render_cycle_rows_wire (on row_count), before any
+ * pointer is used: capacity and workspace return -1, the others
+ * RM_ERR_INVALID_ARGUMENT (rm_wire_decode_parts for any of its parts). */
 int64_t rm_wire_capacity(int W, int nrows);
 int64_t rm_wire_workspace_bytes(int W, int nrows);
 rm_status rm_wire_encode(rm_ctx *ctx, int W, int nrows, const uint32_t *rows, uint8_t *msg, void *workspace,

@@ -420,6 +420,18 @@ int rows_of_part(int H, const RowPart &p) {
     return (int)(full * p.run + tail);
 }
 
+// The compressed wire's one size rule (include/rm.h), checked by every entry
+// point that sizes, writes or reads a message before it touches a pointer: a
+// part of nrows rows of W pixels must fit the launches (tile rows in grid.y)
+// and the table entry's 27-bit word offset (rm_wire.hip: off << 5 | cnt), for
+// a message whose every tile takes all of its kTileWords words.
+bool wire_part_ok(int W, int nrows) {
+    if (W <= 0 || W > (1 << 18) || nrows < 0 || nrows > 65535) return false;
+    const int64_t T = (int64_t)((W + 7) / 8) * ((nrows + 7) / 8);
+    const int64_t words = ((int64_t)rm::wire_capacity(W, nrows) - 8 - ((4 * T + 7) & ~(int64_t)7)) / 8;  // kTileWords T
+    return words < ((int64_t)1 << 27);
+}
+
 int pick_kernel(const rm_ctx *c);
 
 FrameConst frame_const(const rm_ctx *c, int W, int H, const RowPart &part, int nrows) {
@@ -1122,7 +1134,7 @@ rm_status rm_render_cycle_rows_wire(rm_ctx *ctx, int W, int H, int cycle, int of
                                     int row_count, uint8_t *msg, void *workspace, int64_t *size_out, rm_stats *stats) {
     RowPart p;
     if (!ctx) return RM_ERR_INVALID_ARGUMENT;
-    if (!cycle_part(cycle, offset, run, p) || row_count < 0 || !msg || !workspace || W <= 0 || W > (1 << 18))
+    if (!wire_part_ok(W, row_count) || !cycle_part(cycle, offset, run, p) || !msg || !workspace)
         return fail(ctx, RM_ERR_INVALID_ARGUMENT, "rm_render_cycle_rows_wire: bad arguments");
     if (ctx->scene < 0) return fail(ctx, RM_ERR_NO_SCENE, "no scene loaded (rm_load_scene)");
     if (ctx->scene == rm::SCENE_PLUGIN)
@@ -1178,17 +1190,17 @@ rm_status rm_deinterleave_cycle_rgb8(rm_ctx *ctx, int W, int H, int cycle, int n
 }
 
 int64_t rm_wire_capacity(int W, int nrows) {
-    return (W <= 0 || W > (1 << 18) || nrows < 0) ? -1 : (int64_t)rm::wire_capacity(W, nrows);
+    return wire_part_ok(W, nrows) ? (int64_t)rm::wire_capacity(W, nrows) : -1;
 }
 
 int64_t rm_wire_workspace_bytes(int W, int nrows) {
-    return (W <= 0 || W > (1 << 18) || nrows < 0) ? -1 : (int64_t)rm::wire_workspace(W, nrows);
+    return wire_part_ok(W, nrows) ? (int64_t)rm::wire_workspace(W, nrows) : -1;
 }
 
 rm_status rm_wire_encode(rm_ctx *ctx, int W, int nrows, const uint32_t *rows, uint8_t *msg, void *workspace,
                          int64_t *size_out) {
     if (!ctx) return RM_ERR_INVALID_ARGUMENT;
-    if (W <= 0 || W > (1 << 18) || nrows < 0 || nrows > 65535 || !msg || !workspace || (nrows > 0 && !rows))
+    if (!wire_part_ok(W, nrows) || !msg || !workspace || (nrows > 0 && !rows))
         return fail(ctx, RM_ERR_INVALID_ARGUMENT, "rm_wire_encode: bad arguments");
     if (!is_device_ptr(msg) || !is_device_ptr(workspace) || (nrows > 0 && !is_device_ptr(rows)) ||
         (size_out && !is_device_ptr(size_out)))
@@ -1204,8 +1216,8 @@ rm_status rm_wire_decode(rm_ctx *ctx, int W, int H, int cycle, int offset, int r
                          uint32_t *frame) {
     RowPart p;
     if (!ctx) return RM_ERR_INVALID_ARGUMENT;
-    if (W <= 0 || W > (1 << 18) || H <= 0 || !cycle_part(cycle, offset, run, p) || nrows < 0 || nrows > 65535 ||
-        nrows > rows_of_part(H, p) || !msg || !frame)
+    if (!wire_part_ok(W, nrows) || H <= 0 || !cycle_part(cycle, offset, run, p) || nrows > rows_of_part(H, p) ||
+        !msg || !frame)
         return fail(ctx, RM_ERR_INVALID_ARGUMENT, "rm_wire_decode: bad arguments");
     if (!is_device_ptr(msg) || !is_device_ptr(frame))
         return fail(ctx, RM_ERR_INVALID_ARGUMENT, "rm_wire_decode: device pointers required");
@@ -1227,7 +1239,7 @@ rm_status rm_wire_decode_parts(rm_ctx *ctx, int W, int H, int cycle, int nparts,
     parts.cycle = cycle;
     for (int i = 0; i < nparts; i++) {
         RowPart p;
-        if (!cycle_part(cycle, offsets[i], runs[i], p) || nrows[i] < 0 || nrows[i] > 65535 ||
+        if (!wire_part_ok(W, nrows[i]) || !cycle_part(cycle, offsets[i], runs[i], p) ||
             nrows[i] > rows_of_part(H, p) || !msgs[i] || !is_device_ptr(msgs[i]))
             return fail(ctx, RM_ERR_INVALID_ARGUMENT, "rm_wire_decode_parts: bad part");
         parts.part[i] = rm::WirePart{msgs[i], nrows[i], offsets[i], runs[i]};

@@ -62,7 +62,9 @@ __global__ __launch_bounds__(1024) void rm_wire_tile_scan(const uint8_t* __restr
         }
         return s;
     };
-    uint32_t s = 0;  // (the payload's words: < 2^27, the table's offset field)
+    // (the payload's words: < 2^27, the table's offset field; every entry point refuses larger parts:
+    // wire_part_ok, rm_capi.cpp)
+    uint32_t s = 0;
     for (long long c = c0; c < c1; c++) s += chunk_sum(c);
     uint32_t x = s;  // inclusive scan over the wave's lanes
 #pragma unroll

@@ -73,6 +73,79 @@ def encode(rows):
     return out
 
 
+_BIT_LENGTH = np.array([int(v).bit_length() for v in range(256)], np.int64)
+
+
+def encode_fast(rows):
+    """encode(rows), byte for byte, in whole-array numpy: `encode` above is the
+    specification, this is the same format fast enough for parts of 10^5 tiles
+    (tests/test_wire.py pins the two together)."""
+    rows = np.ascontiguousarray(rows, np.uint32)
+    tiles, TX, TY = _tiles(rows)
+    T = TX * TY
+    bs, planes = [], []  # per channel: the widths [T]; per (channel, bit): the plane words [T]
+    for c in range(3):
+        v = ((tiles >> np.uint32(8 * c)) & np.uint32(255)).astype(np.int16).reshape(T, 8, 8)
+        ref = np.empty_like(v)
+        ref[:, :, 1:] = v[:, :, :-1]
+        ref[:, 1:, 0] = v[:, :-1, 0]
+        ref[:, 0, 0] = v[:, 0, 0]
+        s = (((v - ref) & 255) ^ 128) - 128  # int8 wrap
+        z = np.where(s >= 0, 2 * s, -2 * s - 1).astype(np.uint8).reshape(T, 64)
+        z[:, 0] = 0
+        bs.append(_BIT_LENGTH[z.max(axis=1)] if T else np.zeros(0, np.int64))
+        # bit i of the 64 lanes as one little-endian word: lane l is bit l
+        planes.append([np.packbits((z >> i) & 1, axis=1, bitorder="little").view("<u8").reshape(T)
+                       for i in range(8)])
+    counts = 1 + bs[0] + bs[1] + bs[2]
+    offs = np.cumsum(counts) - counts
+    total = int(counts.sum())
+    flat = np.zeros(total, np.uint64)
+    flat[offs] = ((tiles[:, 0] & np.uint32(0xFFFFFF)).astype(np.uint64) | (bs[0].astype(np.uint64) << np.uint64(24)) |
+                  (bs[1].astype(np.uint64) << np.uint64(28)) | (bs[2].astype(np.uint64) << np.uint64(32)))
+    first = offs + 1  # the channel's first plane word
+    for c in range(3):
+        for i in range(8):
+            has = bs[c] > i
+            flat[first[has] + i] = planes[c][i][has]
+        first = first + bs[c]
+    hb = header_bytes(T)
+    out = np.zeros(hb + 8 * total, np.uint8)
+    out[:8] = np.frombuffer(np.array([hb + 8 * total], np.int64).tobytes(), np.uint8)
+    out[8:8 + 4 * T] = np.frombuffer(((offs << 5) | counts).astype(np.uint32).tobytes(), np.uint8)
+    out[hb:] = np.frombuffer(flat.astype("<u8").tobytes(), np.uint8)
+    return out
+
+
+def first_difference(got, ref, T):
+    """Where two messages of a T-tile part first differ, in a line (None when
+    equal): the size word, the first differing table entry, or the first
+    differing payload word and the tile of `ref` that owns it."""
+    got, ref = np.asarray(got, np.uint8), np.asarray(ref, np.uint8)
+    if got.size == ref.size and np.array_equal(got, ref):
+        return None
+    hb = header_bytes(T)
+    if min(got.size, ref.size) < hb:
+        return f"sizes {got.size} != {ref.size}: shorter than the {hb}-byte header of {T} tiles"
+    size = [int(np.frombuffer(m[:8].tobytes(), np.int64)[0]) for m in (got, ref)]
+    tab = [np.frombuffer(m[8:8 + 4 * T].tobytes(), np.uint32) for m in (got, ref)]
+    at = np.flatnonzero(tab[0] != tab[1])
+    if at.size:
+        t = int(at[0])
+        return (f"table: tile {t} of {T} is offset {int(tab[0][t]) >> 5} count {int(tab[0][t]) & 31}, expected offset "
+                f"{int(tab[1][t]) >> 5} count {int(tab[1][t]) & 31} ({at.size} entries differ; size words {size[0]}, "
+                f"expected {size[1]})")
+    k = (min(got.size, ref.size) - hb) & ~7
+    pay = [np.frombuffer(m[hb:hb + k].tobytes(), np.uint64) for m in (got, ref)]
+    at = np.flatnonzero(pay[0] != pay[1])
+    if at.size:
+        w = int(at[0])
+        t = int(np.searchsorted(tab[1] >> 5, w, side="right")) - 1
+        return (f"payload: word {w} (tile {t} of {T}, its word {w - (int(tab[1][t]) >> 5)}) is {int(pay[0][w]):#018x}, "
+                f"expected {int(pay[1][w]):#018x} ({at.size} words differ)")
+    return f"sizes {got.size} != {ref.size} (size words {size[0]}, expected {size[1]}); equal up to the shorter"
+
+
 def decode(msg, n, W):
     """message -> uint32 [n, W] RGBA8 words (alpha 255)."""
     msg = np.asarray(msg, np.uint8)
