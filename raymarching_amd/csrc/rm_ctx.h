@@ -1,0 +1,178 @@
+// rm_ctx.h -- the context behind the C ABI (include/rm.h) and what the host
+// files of librm.so share about it: rm_capi.cpp (entry points),
+// rm_render_host.cpp (a render launch), rm_ctx_streams.cpp (stream and event
+// lifetime).  Internal; other translation units go through rm_internal.h.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <set>
+#include <string>
+#include <vector>
+
+#include "../../include/rm.h"
+#include "rm_launch.h"
+#include "rm_plugin_host.h"
+#include "rm_rows.h"
+
+struct rm_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    int scene = -1;
+    std::string scene_file;
+    // uniforms (common.frag:4-11)
+    float res[2] = {0.0f, 0.0f};
+    bool res_set = false;
+    float pos[3] = {0.0f, 0.0f, 0.0f};
+    float mouse[2] = {0.0f, 0.0f};
+    float time = 0.0f;
+    // KERNEL_PERSIST: blocks of self-resetting tile counters, one per stream
+    // the context launches on (launches on one stream run one after another, so
+    // a block is never shared by two launches in flight).  At most kPersistBlocks:
+    // a new stream takes the least recently used block once the event recorded
+    // after its last launch has completed (the launch left its counters zeroed).
+    struct PersistBlock {
+        hipStream_t stream = nullptr;
+        uint32_t *ctr = nullptr;
+        hipEvent_t last = nullptr;
+        uint64_t used = 0;
+    };
+    static constexpr int kPersistBlocks = 4;
+    std::vector<PersistBlock> persist;
+    // work this context enqueued: `dirty` is set by each call that enqueues
+    // on `stream`; `done` is recorded on the stream only when the context
+    // leaves it (rm_set_stream) or is destroyed -- an event recorded after
+    // every launch cost a ~11 us gap between consecutive frames on the stream
+    // (DESIGN.md 2.14).  A left stream's event stays in `retired` until it
+    // completes (rm_destroy waits for these, not the
+    // whole device).
+    hipEvent_t done = nullptr;
+    bool dirty = false;
+    std::vector<hipEvent_t> retired;
+    // streams bound with rm_set_stream_kept (the caller keeps them alive until
+    // rm_destroy): leaving one records nothing; it joins `owed`, and its work
+    // is marked only when something waits for it (an entry's release,
+    // rm_destroy), on the stream itself
+    std::vector<hipStream_t> kept, owed;
+    float sample_part = 1.0f;  // u_sample_part, u_seed1, u_seed2: read by rm_render_accumulate*
+    float seed1[2] = {0.0f, 0.0f}, seed2[2] = {0.0f, 0.0f};
+    rm_params params = {128, 0, 0, 0, 1};
+    std::string err;
+    std::set<std::string> warned;
+    unsigned long long *d_evals = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    float4 *staging = nullptr;
+    size_t staging_bytes = 0;
+    uint32_t *mips = nullptr;  // bloom's mip levels 1..d2
+    size_t mips_texels = 0;
+    int bloom_runs_w = 0, bloom_runs_h = 0;  // the size whose bloom run tables `mips` holds (0: none)
+    hipStream_t bloom_runs_stream = nullptr;
+    // the scratch buffer is shared by the context's streams: when the context
+    // leaves the stream of its last bloom / post chain (bloom_stream), bloom_ev
+    // is recorded there, and a bloom on another stream first waits for it (no
+    // marker per frame; one per leave, and only after a bloom)
+    hipEvent_t bloom_ev = nullptr;
+    hipStream_t bloom_stream = nullptr;
+    bool bloom_pending = false;  // a bloom ran on bloom_stream since bloom_ev was last recorded
+    rmplugin::Module plugin;  // the loaded scene plugin (scene == SCENE_PLUGIN)
+    uint32_t *tile_order = nullptr;  // rm_set_tile_order (device copy)
+    int64_t tile_order_n = 0;
+    // adaptive dispatch order (rm_params.schedule): per launch geometry and
+    // stream, the tile durations of the last launch and the order they give
+    // Every kSchedPeriod-th launch of a geometry (L_s = s * period, s = 0, 1,
+    // ...) writes its tile durations into cost[s & 1]; sort s of those
+    // durations runs right after it on the same stream and writes order[s & 1],
+    // which launches L_s + 1 .. L_{s+1} dispatch.  The other launches write no
+    // durations.  (Round 2-4 sorted on a side stream, overlapping the next
+    // launch: its kernels only got CUs as that launch drained, and the launch
+    // after it waited ~45 us for them)
+    struct Sched {
+        uint64_t key = 0;
+        hipStream_t stream = nullptr;
+        int n = 0, gx = 0;         // tiles, tile-grid width
+        uint64_t k = 0;            // launches so far
+        uint32_t *buf = nullptr;   // cost[2][n] | order[2][n] | 2 x (hist[256] | cursor[256]) | bucket u8[n]
+        hipEvent_t last = nullptr;  // after the last launch that read or wrote buf: recorded on `stream`
+        bool dirty = false;         // when the entry is released or the context destroyed on `stream`
+        // ... or, once the context has left `stream`, the `done` event recorded
+        // there as it left (borrowed: one marker per leave instead of one per
+        // entry as well; rm_destroy destroys it after the entries are released)
+        hipEvent_t left = nullptr;
+        uint64_t used = 0;
+        size_t bytes = 0;  // buf's size
+    };
+    Sched sched[8];
+    uint64_t sched_clock = 0;
+    // buffers of evicted adaptive-order entries, each with the marker of its
+    // last use (ev: owned, or a borrowed `done` event); reused by a new entry
+    // once the marker has completed, instead of a host wait at the eviction
+    // (a marker recorded then on a kept stream covers everything queued there
+    // since, e.g. the next pipelined frame)
+    struct Spare {
+        uint32_t *buf = nullptr;
+        size_t bytes = 0;
+        hipEvent_t ev = nullptr;
+        bool own = false;
+    };
+    std::vector<Spare> spare;
+};
+
+namespace rmhost {
+
+inline rm_status fail(rm_ctx *c, rm_status s, const std::string &msg) {
+    if (c) c->err = msg;
+    return s;
+}
+
+inline rm_status hip_fail(rm_ctx *c, hipError_t e, const char *what) {
+    return fail(c, e == hipErrorOutOfMemory ? RM_ERR_OUT_OF_MEMORY : RM_ERR_DEVICE,
+                std::string(what) + ": " + hipGetErrorString(e));
+}
+
+#define RM_HIP(call)                                          \
+    do {                                                      \
+        hipError_t e_ = (call);                               \
+        if (e_ != hipSuccess) return hip_fail(ctx, e_, #call); \
+    } while (0)
+
+// Note that the context enqueued work on its stream (rm_ctx::dirty).
+inline void mark_done(rm_ctx *ctx) { ctx->dirty = true; }
+
+inline bool is_kept(const rm_ctx *ctx, hipStream_t s) {
+    for (hipStream_t k : ctx->kept)
+        if (k == s) return true;
+    return false;
+}
+
+inline bool is_device_ptr(const void *p) {
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
+}
+
+// ---- rm_ctx_streams.cpp
+rm_status persist_block(rm_ctx *ctx, rm_ctx::PersistBlock *&out);
+rm_ctx::Sched *sched_slot(rm_ctx *ctx, int W, int H, const rm::RowPart &part, int row0, int count, rm_status &st);
+hipError_t sched_release(rm_ctx *ctx, rm_ctx::Sched &e);
+rm_status set_stream(rm_ctx *ctx, hipStream_t s);  // rm_set_stream
+void wait_idle(rm_ctx *ctx);                       // rm_destroy: nothing the context enqueued still runs
+
+// ---- rm_render_host.cpp
+int pick_kernel(const rm_params &p);
+rm::FrameConst frame_const(const rm_ctx *c, int W, int H, const rm::RowPart &part, int nrows);
+// rm_render_cycle_rows_wire: the compressed wire's message instead of pixels
+// (`out` is then the tile-slot workspace, rm_wire_tile.h)
+struct WireOut {
+    uint8_t *msg;
+    long long *size_out;
+};
+rm_status render_dev(rm_ctx *ctx, int W, int H, const rm::RowPart &part, int row0, int count, void *out, bool rgba8,
+                     rm_stats *stats, uint32_t *evmap = nullptr, bool accum = false, const WireOut *wire = nullptr);
+rm_status render_part(rm_ctx *ctx, int W, int H, const rm::RowPart &part, int row_begin, int row_count, void *out,
+                      bool rgba8, rm_stats *stats, uint32_t *evmap = nullptr, bool accum = false);
+rm_status render_any(rm_ctx *ctx, int W, int H, int band, int nshards, int shard, int row_begin, int row_count,
+                     void *out, bool rgba8, rm_stats *stats, uint32_t *evmap = nullptr, bool accum = false);
+
+}  // namespace rmhost

@@ -81,7 +81,7 @@ __device__ __forceinline__ int div_by(int a, uint32_t m, int d) {
     return m ? (int)__umulhi((uint32_t)a, m) : a / d;
 }
 
-// Buckets of the adaptive dispatch order (rm_capi.cpp, rm_kernels.hip): 256
+// Buckets of the adaptive dispatch order (rm_render_host.cpp, rm_kernels.hip): 256
 // logarithmic buckets of a tile's duration, 8 per octave of shader clocks
 // (float exponent and 3 mantissa bits), bucket 0 = costliest.
 constexpr int kSchedBuckets = 256;

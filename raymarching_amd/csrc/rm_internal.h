@@ -1,4 +1,4 @@
-// rm_internal.h -- librm.so-internal accessors of a context (rm_capi.cpp) for
+// rm_internal.h -- librm.so-internal accessors of a context (rm_ctx.h) for
 // the other translation units of the library (rm_comm.cpp).  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>

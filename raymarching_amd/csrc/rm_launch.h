@@ -1,4 +1,4 @@
-// rm_launch.h -- host-side launcher interface between the C-ABI (rm_capi.cpp)
+// rm_launch.h -- host-side launcher interface between the host files (rm_ctx.h)
 // and the kernels (rm_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>

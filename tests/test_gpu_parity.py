@@ -439,7 +439,7 @@ def timed_path_equals_instrumented(r, scene, W, H, img, launches=10):
     _, st8 = r.render_rgba8(W, H, out=out8, stats=True)
     assert st8["dispatch"] == "adaptive", st8
     ntiles = ((W + 7) // 8) * ((H + 7) // 8)
-    if scene == "T":  # (latency tiles only in launches of <= 98304 tiles: rm_capi.cpp lat_tiles_for)
+    if scene == "T":  # (latency tiles only in launches of <= 98304 tiles: rm_render_host.cpp lat_tiles_for)
         assert st8["lat_tiles"] == (min(2048, ntiles) if ntiles <= 98304 else 0), st8
     else:
         assert st8["lat_tiles"] == 0, st8

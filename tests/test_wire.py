@@ -423,7 +423,7 @@ def test_gpu_render_epilogue_message_above_the_kernel_switch(R, torch_cuda, scen
     n = rm.cycle_rows(H, cycle, offset, run)
     TX, TY = _tile_grid(n, W)
     T = TX * TY
-    lat_max = _csrc_constant("kLatMaxTiles", "rm_capi.cpp")
+    lat_max = _csrc_constant("kLatMaxTiles", "rm_render_host.cpp")
     assert T > _csrc_constant("kDirectTiles")
     assert TY > _decode_grid(W, [n])[1]
     if case == "three_chunks_no_latency_tiles":

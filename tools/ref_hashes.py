@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Fingerprints of the reference's shader files, for rm_load_scene's reload
-semantics (raymarching_amd/csrc/rm_capi.cpp, "scene files of registered
+semantics (raymarching_amd/csrc/rm_scene_file.cpp, "scene files of registered
 names").  Build container only (reads /root/reference); prints the constants
-rm_capi.cpp holds.  Only 64-bit hashes are kept, never the text.
+rm_scene_file.cpp holds.  Only 64-bit hashes are kept, never the text.
 
 A fingerprint is FNV-1a 64 over the file's bytes with every whitespace byte
 removed (line endings and indentation do not matter).  output_shader.frag is
