@@ -1,6 +1,6 @@
 // rm_comm.cpp -- row-sharded frames across GPUs over RCCL (include/rm.h,
 // "Multi-GPU").  SURVEY.md 8(b)/8(e): rank r renders the frame rows y with
-// (y / band) % nranks == r (rm_render_band_rgba8: RGBA8 packed in the kernel
+// (y / band) % nranks == r (rm_render_cycle_rows_rgba8: RGBA8 packed in the kernel
 // epilogue), drops the alpha byte (rm_pack_rgb8: the pass writes alpha 1,
 // output_shader.frag:419), one ncclGather brings the 3 B/px bands to rank 0
 // over xGMI, and rank 0 de-interleaves them into the RGBA8 frame
@@ -91,11 +91,14 @@ struct rm_comm {
     size_t band_bytes = 0, wire_bytes = 0, gathered_bytes = 0;
     // render start / render end / gather end / de-interleave end (rm_stats)
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
+    // the rows this rank renders and the rows it sends: bands travel as equal
+    // slots of the largest shard's rows (ncclGather), weighted parts unpadded
     int rows_mine = 0, rows_per_shard = 0;
-    // weighted parts (rm_render_sharded_runs): every rank's rows and the byte
-    // offset of its rows in the unpadded gathered buffer
     bool weighted = false;
-    std::vector<int> rows_of, base_of;
+    // every rank's rows, and where they start in the root's gathered buffer
+    // (in rows): r * rows_per_shard for padded slots, else the parts back to back
+    std::vector<int> rows_of;
+    std::vector<int64_t> base_of;
 };
 
 namespace {
@@ -144,25 +147,23 @@ rm_status comm_new(rm_comm **out, rm_ctx *ctx, int nranks, int rank) {
     return RM_OK;
 }
 
-// How the frame's rows are dealt: round-robin bands of `band` rows, or (runs
-// non-null) weighted cyclic parts, rank r owning a run of runs[r] rows in every
-// cycle of sum(runs) rows, the runs in rank order.
+// How the frame's rows are dealt: rank r owns a run of run[r] rows at off[r] in
+// every cycle of `cycle` rows, the runs in rank order (rm_rows.h).  Round-robin
+// bands (band > 0) are the case run[r] = band; weighted parts have band 0.
 struct Split {
-    int band = 0;
-    const int *runs = nullptr;
-    int cycle = 0;
-    std::vector<int> off;
+    int band = 0, cycle = 0;
+    std::vector<int> off, run;
 };
 rm_status make_split(rm_comm *c, int band, const int *runs, Split &sp) {
-    sp.band = band;
-    sp.runs = runs;
-    if (!runs) return band > 0 ? RM_OK : RM_ERR_INVALID_ARGUMENT;
-    long long cyc = 0;
+    sp.band = runs ? 0 : band;
     sp.off.assign(c->nranks, 0);
+    sp.run.assign(c->nranks, 0);
+    long long cyc = 0;
     for (int r = 0; r < c->nranks; r++) {
-        if (runs[r] < 1) return RM_ERR_INVALID_ARGUMENT;
+        sp.run[r] = runs ? runs[r] : band;
+        if (sp.run[r] < 1) return RM_ERR_INVALID_ARGUMENT;
         sp.off[r] = (int)cyc;
-        cyc += runs[r];
+        cyc += sp.run[r];
         if (cyc > 0x7fffffffLL) return RM_ERR_INVALID_ARGUMENT;
     }
     sp.cycle = (int)cyc;
@@ -173,31 +174,22 @@ rm_status make_split(rm_comm *c, int band, const int *runs, Split &sp) {
 rm_status enqueue_local(rm_comm *c, int W, int H, const Split &sp) {
     rm_ctx *ctx = c->ctx;
     rm_status st = RM_OK;
-    size_t wire_bytes = 0, gathered_bytes = 0;
-    c->weighted = sp.runs != nullptr;
-    if (!c->weighted) {
-        rm_shard_layout L;
-        st = rm_sharded_layout(W, H, sp.band, c->nranks, c->rank, &L);
-        if (st != RM_OK) return comm_fail(c, st, "rm_render_sharded: bad size/band");
-        c->rows_mine = L.rows_mine;
-        c->rows_per_shard = L.rows_per_shard;
-        wire_bytes = (size_t)L.wire_bytes;
-        gathered_bytes = (size_t)L.gathered_bytes;
-    } else {
-        c->rows_of.assign(c->nranks, 0);
-        c->base_of.assign(c->nranks, 0);
-        int total = 0;
-        for (int r = 0; r < c->nranks; r++) {
-            st = rm_cycle_rows(H, sp.cycle, sp.off[r], sp.runs[r], &c->rows_of[r]);
-            if (st != RM_OK) return comm_fail(c, st, "rm_render_sharded_runs: bad size/runs");
-            c->base_of[r] = total;
-            total += c->rows_of[r];
-        }
-        c->rows_mine = c->rows_of[c->rank];
-        c->rows_per_shard = c->rows_mine;
-        wire_bytes = (size_t)c->rows_mine * 3 * W;
-        gathered_bytes = (size_t)H * 3 * W;  // every row once, rank by rank
+    c->weighted = sp.band == 0;
+    c->rows_of.assign(c->nranks, 0);
+    c->base_of.assign(c->nranks, 0);
+    int most = 0;
+    for (int r = 0; r < c->nranks; r++) {
+        st = rm_cycle_rows(H, sp.cycle, sp.off[r], sp.run[r], &c->rows_of[r]);
+        if (st != RM_OK) return comm_fail(c, st, "rm_render_sharded: bad size/band/runs");
+        most = c->rows_of[r] > most ? c->rows_of[r] : most;
     }
+    c->rows_mine = c->rows_of[c->rank];
+    c->rows_per_shard = c->weighted ? c->rows_mine : most;
+    for (int r = 1; r < c->nranks; r++)
+        c->base_of[r] = c->weighted ? c->base_of[r - 1] + c->rows_of[r - 1] : (int64_t)r * most;
+    const size_t wire_bytes = (size_t)c->rows_per_shard * 3 * W;
+    // weighted: every row once, rank by rank
+    const size_t gathered_bytes = c->weighted ? (size_t)H * 3 * W : wire_bytes * c->nranks;
     const int n = c->rows_mine;
     if (hipSetDevice(rm_internal_device(ctx)) != hipSuccess) return comm_fail(c, RM_ERR_DEVICE, "hipSetDevice");
     st = grow(c, c->band, c->band_bytes, (size_t)c->rows_per_shard * W * 4);
@@ -207,18 +199,46 @@ rm_status enqueue_local(rm_comm *c, int W, int H, const Split &sp) {
     hipStream_t s = rm_internal_stream(ctx);
     if (hipEventRecord(c->ev0, s) != hipSuccess) return comm_fail(c, RM_ERR_DEVICE, "hipEventRecord");
     if (n > 0) {
-        st = c->weighted ? rm_render_cycle_rows_rgba8(ctx, W, H, sp.cycle, sp.off[c->rank], sp.runs[c->rank], 0, n,
-                                                      c->band, nullptr)
-                         : rm_render_band_rgba8(ctx, W, H, sp.band, c->nranks, c->rank, c->band, nullptr);
+        st = rm_render_cycle_rows_rgba8(ctx, W, H, sp.cycle, sp.off[c->rank], sp.run[c->rank], 0, n, c->band, nullptr);
         if (st != RM_OK) return st;
     }
     if (hipEventRecord(c->ev1, s) != hipSuccess) return comm_fail(c, RM_ERR_DEVICE, "hipEventRecord");
     return rm_pack_rgb8(ctx, (int64_t)n * W, c->band, c->wire);
 }
 
-rm_status enqueue_gather_ops(rm_comm *c, int W);
+// the gather of every rank's wire into rank 0's gathered buffer
+rm_status enqueue_gather_ops(rm_comm *c, int W) {
+    if (!c->nc) return RM_OK;  // a one-rank communicator without RCCL: the wire is the gathered buffer
+    rm::TraceRange range("rm_gather");
+    Rccl *R = rccl();
+    hipStream_t s = rm_internal_stream(c->ctx);
+    const size_t row = (size_t)3 * W;
+    if (!c->weighted && R->Gather)
+        return nccl_check(c, R->Gather(c->wire, c->rank == 0 ? c->gathered : nullptr, c->rows_per_shard * row,
+                                       kNcclUint8, 0, c->nc, s), "ncclGather");
+    // grouped point-to-point: the padded slots as ncclGather moves them, or the
+    // weighted parts unpadded (an empty one is skipped)
+    auto bytes = [&](int r) { return (c->weighted ? c->rows_of[r] : c->rows_per_shard) * row; };
+    rm_status st = nccl_check(c, R->GroupStart(), "ncclGroupStart");
+    if (st != RM_OK) return st;
+    if (c->rank == 0) {
+        for (int r = 1; r < c->nranks && st == RM_OK; r++)
+            if (bytes(r))
+                st = nccl_check(c, R->Recv(c->gathered + c->base_of[r] * row, bytes(r), kNcclUint8, r, c->nc, s),
+                                "ncclRecv");
+    } else if (bytes(c->rank)) {
+        st = nccl_check(c, R->Send(c->wire, bytes(c->rank), kNcclUint8, 0, c->nc, s), "ncclSend");
+    }
+    rm_status st2 = nccl_check(c, R->GroupEnd(), "ncclGroupEnd");
+    if (st != RM_OK) return st;
+    if (st2 != RM_OK) return st2;
+    if (c->rank == 0 && bytes(0) &&
+        hipMemcpyAsync(c->gathered, c->wire, bytes(0), hipMemcpyDeviceToDevice, s) != hipSuccess)
+        return comm_fail(c, RM_ERR_DEVICE, "gather copy");
+    return RM_OK;
+}
 
-// the gather of every rank's wire into rank 0's gathered buffer, then ev2
+// the gather, then its end event (ev2)
 rm_status enqueue_gather(rm_comm *c, int W) {
     rm_status st = enqueue_gather_ops(c, W);
     if (st != RM_OK) return st;
@@ -227,63 +247,17 @@ rm_status enqueue_gather(rm_comm *c, int W) {
     return rm_internal_mark_done(c->ctx);
 }
 
-rm_status enqueue_gather_ops(rm_comm *c, int W) {
-    if (!c->nc) return RM_OK;  // a one-rank communicator without RCCL: the wire is the gathered buffer
-    rm::TraceRange range("rm_gather");
-    Rccl *R = rccl();
-    hipStream_t s = rm_internal_stream(c->ctx);
-    if (c->weighted) {  // unequal parts: grouped point-to-point, unpadded
-        const size_t row = (size_t)3 * W;
-        rm_status st = nccl_check(c, R->GroupStart(), "ncclGroupStart");
-        if (st != RM_OK) return st;
-        if (c->rank == 0) {
-            for (int r = 1; r < c->nranks && st == RM_OK; r++)
-                if (c->rows_of[r] > 0)
-                    st = nccl_check(c, R->Recv(c->gathered + (size_t)c->base_of[r] * row, (size_t)c->rows_of[r] * row,
-                                               kNcclUint8, r, c->nc, s), "ncclRecv");
-        } else if (c->rows_mine > 0) {
-            st = nccl_check(c, R->Send(c->wire, (size_t)c->rows_mine * row, kNcclUint8, 0, c->nc, s), "ncclSend");
-        }
-        rm_status st2 = nccl_check(c, R->GroupEnd(), "ncclGroupEnd");
-        if (st != RM_OK) return st;
-        if (st2 != RM_OK) return st2;
-        if (c->rank == 0 && c->rows_mine > 0 &&
-            hipMemcpyAsync(c->gathered, c->wire, (size_t)c->rows_mine * row, hipMemcpyDeviceToDevice, s) != hipSuccess)
-            return comm_fail(c, RM_ERR_DEVICE, "gather copy");
-        return RM_OK;
-    }
-    const size_t bytes = (size_t)c->rows_per_shard * 3 * W;
-    if (R->Gather)
-        return nccl_check(c, R->Gather(c->wire, c->rank == 0 ? c->gathered : nullptr, bytes, kNcclUint8, 0, c->nc, s),
-                          "ncclGather");
-    // grouped point-to-point form of the gather
-    rm_status st = nccl_check(c, R->GroupStart(), "ncclGroupStart");
-    if (st != RM_OK) return st;
-    if (c->rank == 0) {
-        for (int r = 1; r < c->nranks && st == RM_OK; r++)
-            st = nccl_check(c, R->Recv(c->gathered + (size_t)r * bytes, bytes, kNcclUint8, r, c->nc, s), "ncclRecv");
-    } else {
-        st = nccl_check(c, R->Send(c->wire, bytes, kNcclUint8, 0, c->nc, s), "ncclSend");
-    }
-    rm_status st2 = nccl_check(c, R->GroupEnd(), "ncclGroupEnd");
-    if (st != RM_OK) return st;
-    if (st2 != RM_OK) return st2;
-    if (c->rank == 0 && hipMemcpyAsync(c->gathered, c->wire, bytes, hipMemcpyDeviceToDevice, s) != hipSuccess)
-        return comm_fail(c, RM_ERR_DEVICE, "gather copy");
-    return RM_OK;
-}
-
 rm_status finish(rm_comm *c, int W, int H, const Split &sp, uint32_t *frame, rm_stats *stats) {
     rm_status st = RM_OK;
     rm::TraceRange range("rm_deinterleave");
-    if (c->rank == 0 && c->weighted) {
+    const uint8_t *rows = c->nc ? c->gathered : c->wire;
+    if (c->rank == 0 && c->weighted) {  // parts back to back
         std::vector<int64_t> bytes(c->nranks);
-        for (int r = 0; r < c->nranks; r++) bytes[r] = (int64_t)c->base_of[r] * 3 * W;
-        st = rm_deinterleave_cycle_rgb8(c->ctx, W, H, sp.cycle, c->nranks, sp.off.data(), sp.runs, bytes.data(),
-                                        c->nc ? c->gathered : c->wire, frame);
-    } else if (c->rank == 0) {
-        st = rm_deinterleave_rgb8(c->ctx, W, H, sp.band, c->nranks, c->rows_per_shard,
-                                  c->nc ? c->gathered : c->wire, frame);
+        for (int r = 0; r < c->nranks; r++) bytes[r] = c->base_of[r] * 3 * W;
+        st = rm_deinterleave_cycle_rgb8(c->ctx, W, H, sp.cycle, c->nranks, sp.off.data(), sp.run.data(), bytes.data(),
+                                        rows, frame);
+    } else if (c->rank == 0) {  // padded slots
+        st = rm_deinterleave_rgb8(c->ctx, W, H, sp.band, c->nranks, c->rows_per_shard, rows, frame);
     }
     if (st != RM_OK) return st;
     if (c->rank == 0 && hipEventRecord(c->ev3, rm_internal_stream(c->ctx)) != hipSuccess)

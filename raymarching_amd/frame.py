@@ -4,8 +4,9 @@ Pixels are independent, so a frame shards by rows.  Rows are dealt to ranks
 in bands of ``band`` rows, round robin: rank r owns frame row y iff
 ``(y // band) % nshards == r`` (cheap sky rows and expensive sponge / floor
 rows spread evenly).  Each rank renders its rows packed in
-increasing y (``rm_render_rows``, or ``rm_render_rows_rgba8``, whose kernel
-packs RGBA8 in its epilogue), and one gather brings every band to the root, where
+increasing y (``rm_render_cycle_rows``, or ``rm_render_cycle_rows_rgba8``, whose
+kernel packs RGBA8 in its epilogue: bands are the cyclic part run = band,
+offset = band * r), and one gather brings every band to the root, where
 ``rm_deinterleave`` writes the frame.  The gather is the only collective on
 the path (``torch.distributed.gather``; the "nccl" backend is RCCL).
 
@@ -222,7 +223,129 @@ class _OnStream:
         return False
 
 
-class DistributedFrame:
+class _Bound:
+    """_OnStream(st) for a frame's own work on its frame stream st: inside,
+    the frame's renderer is bound to st as well; after it (also when the work
+    raised) the renderer is back on the caller's stream."""
+    __slots__ = ("fr", "st", "prev")
+
+    def __init__(self, fr, st):
+        self.fr, self.st = fr, st
+
+    def __enter__(self):
+        import torch
+        self.fr._bind(self.st)
+        self.prev = torch.cuda.current_stream(self.st.device)
+        torch.cuda.set_stream(self.st)
+        return self.st
+
+    def __exit__(self, *exc):
+        import torch
+        torch.cuda.set_stream(self.prev)
+        self.fr.r.set_stream(self.fr.caller)
+        return False
+
+
+class _ShardedFrame:
+    """What the frame loops share: this rank's part of the plan, the frame
+    streams, and submit() / flush() / render() / render_local() around the
+    class's own wire (_complete, _local_part)."""
+
+    def __init__(self, renderer, rank, world, group, plan, streams):
+        import torch
+
+        self.r, self.rank, self.world, self.group, self.plan = renderer, rank, world, group, plan
+        self.dev = dev = torch.device(f"cuda:{renderer.device}")
+        self._pipe = self._pipelined()
+        if streams is None:
+            streams = 2 if self._pipe else 1
+        if streams not in (1, 2):
+            raise ValueError("streams must be 1 or 2")
+        # one stream: the caller's; two: a probed pair that does not share a
+        # hardware queue (on one queue the frames would not overlap)
+        self.caller = torch.cuda.current_stream(dev)
+        self.streams = [self.caller] if streams == 1 else concurrent_streams(dev, streams)
+        if streams > 1:  # the frame streams start after the caller's work so far
+            for st in self.streams:
+                st.wait_stream(self.caller)
+        self.nmine = plan.count(rank)
+        # this rank's rows as every render entry point takes them (round-robin
+        # bands are the cyclic part run = band, offset = band * rank)
+        self._part = (plan.cycle, plan.offsets[rank], plan.part_runs[rank])
+        self.k = 0            # frames submitted
+        self.pending = None   # the frame whose gather / exchange is in flight (_complete's argument)
+
+    def _pipelined(self):
+        import torch.distributed as dist
+        return self.world > 1 and dist.get_backend(self.group) != "gloo"
+
+    def _bind(self, st):
+        """Bind the renderer to frame stream st.  The frame streams other than
+        the caller's come from PyTorch's pool, which never destroys them, so
+        they are bound as kept (rm_set_stream_kept): leaving one records no
+        marker (DESIGN.md 2.14)."""
+        self.r.set_stream(st, kept=st is not self.caller)
+
+    def _native(self, fn, args):
+        """One librm.so call; the per-frame ones have their arguments built
+        once (_render_call): the Python wrappers' checks cost as much host
+        time as a rank's frame takes on the GPU at N = 8."""
+        rc = fn(*args)
+        if rc:
+            from ._lib import check
+            check(rc, self.r._ctx)
+
+    def _render_call(self, dst, j0, j1):
+        """(fn, args) of the render of packed rows [j0, j1) of this rank's part
+        into dst[j0:j1] (float32 [rows, W, 4], or int32 RGBA8 words)."""
+        import ctypes
+
+        import torch
+
+        from ._lib import lib
+        p = self.plan
+        fn = lib().rm_render_cycle_rows if dst.dtype == torch.float32 else lib().rm_render_cycle_rows_rgba8
+        return fn, (self.r._ctx, p.W, p.H, *self._part, j0, j1 - j0, ctypes.c_void_p(dst[j0:j1].data_ptr()), None)
+
+    def _render_into(self, dst, j0, j1, stats=False):
+        """Packed rows [j0, j1) of this rank's part into dst[j0:j1], checked."""
+        p = self.plan
+        return self.r.render_cycle_rows(p.W, p.H, *self._part, j0, j1 - j0, dst[j0:j1], stats=stats)
+
+    def render_local(self, stats=False):
+        """This rank's part only, into slot 0 (no gather), on the first frame
+        stream (whose adaptive tile order the frames use); stats: one
+        synchronous launch.  Ordered before later work on the caller's stream."""
+        st = self.streams[0]
+        with _Bound(self, st):
+            res = self._local_part(stats)
+        if st is not self.caller:
+            self.caller.wait_stream(st)
+        return res
+
+    def flush(self):
+        """Finish the frame in flight (rank 0: its frame is in .frame, ordered
+        before later work on the caller's stream)."""
+        import torch
+
+        if self.pending is not None:
+            item, self.pending = self.pending, None
+            self._complete(item)
+        for st in self.streams[1:]:
+            ev = torch.cuda.Event()
+            ev.record(st)
+            self.streams[0].wait_event(ev)
+        if self.streams[0] is not self.caller:  # ... and the caller's stream after them
+            self.caller.wait_stream(self.streams[0])
+        return self.frame
+
+    def render(self, events=None):
+        """One complete frame (submit + flush)."""
+        self.submit(events)
+        return self.flush()
+
+
+class DistributedFrame(_ShardedFrame):
     """One rank's share of a row-sharded frame on its GPU.
 
     ``render()`` runs this rank's rows, gathers to rank 0 and (on rank 0)
@@ -247,54 +370,45 @@ class DistributedFrame:
     * ``chunks`` > 1 pipelines within a frame: the packed rows are cut into
       that many ranges (same cuts on every rank) and chunk k+1 renders while
       chunk k is gathered; it costs a launch tail per chunk.
+
+    Two wire layouts: round-robin bands travel as equal slots of
+    rows_per_shard rows (one gather, rm_deinterleave*); weighted parts
+    (``runs``) travel unpadded, point to point, back to back in the root's
+    buffer (rm_deinterleave_cycle_rgb8).
     """
 
     def __init__(self, renderer, W, H, band, rank, world, fmt="rgba8", group=None, chunks=1, wire="auto",
                  streams=None, runs=None):
         import torch
 
-        self.r, self.rank, self.world, self.fmt, self.group = renderer, rank, world, fmt, group
         # RGBA8 frames cross the wire as RGB8 (3 B/px: alpha is 1 by construction,
         # rm_pack_rgb8); the root restores alpha while de-interleaving.
         if wire == "auto":
             wire = "rgb8" if fmt == "rgba8" and world > 1 else fmt
         if wire not in (fmt, "rgb8") or (wire == "rgb8" and fmt != "rgba8"):
             raise ValueError(f"wire {wire!r} does not carry {fmt!r} frames")
-        self.wire = wire
-        # one shard: the packed rows are the frame rows (no de-interleave needed)
         if runs is not None and world > 1:
             # weighted parts: unpadded point-to-point gather of RGB8 rows
             if wire != "rgb8":
                 raise ValueError("weighted row parts (runs) need the RGB8 wire (fmt='rgba8')")
-            self.plan = ShardPlan(W, H, band, world, tuple(int(x) for x in runs))
+            plan = ShardPlan(W, H, band, world, tuple(int(x) for x in runs))
         else:
-            self.plan = ShardPlan(W, H, band if world > 1 else H, world)
-        dev = torch.device(f"cuda:{renderer.device}")
-        if streams is None:
-            streams = 2 if self._pipelined() else 1
-        if streams not in (1, 2):
-            raise ValueError("streams must be 1 or 2")
-        # one stream: the caller's; two: a probed pair that does not share a
-        # hardware queue (on one queue the frames would not overlap)
-        self.caller = torch.cuda.current_stream(dev)
-        self.streams = [self.caller] if streams == 1 else concurrent_streams(dev, streams)
-        if streams > 1:  # the frame streams start after the caller's work so far
-            for st in self.streams:
-                st.wait_stream(self.caller)
-        rps = self.plan.rows_per_shard
-        self.nmine = self.plan.count(rank)
+            # one shard: the packed rows are the frame rows (no de-interleave needed)
+            plan = ShardPlan(W, H, band if world > 1 else H, world)
+        self.fmt, self.wire = fmt, wire
+        super().__init__(renderer, rank, world, group, plan, streams)
+        dev = self.dev
+        rps = plan.rows_per_shard
         chunks = max(1, min(int(chunks), rps))
-        if self.plan.weighted:
-            # every shard cuts its own rows into the same number of chunks
-            self.all_cuts = [[round(c * self.plan.count(q) / chunks) for c in range(chunks + 1)]
-                             for q in range(world)]
-            self.cuts = self.all_cuts[rank]
-        else:
-            self.cuts = [round(c * rps / chunks) for c in range(chunks + 1)]
-        nbuf = 2 if world > 1 or streams > 1 else 1
+        # every rank cuts the rows it sends into the same number of chunks: its
+        # own part (weighted), or the padded slot of rows_per_shard rows
+        sent = [plan.count(q) if plan.weighted else rps for q in range(world)]
+        self.all_cuts = [[round(c * n / chunks) for c in range(chunks + 1)] for n in sent]
+        self.cuts = self.all_cuts[rank]
+        nbuf = 2 if world > 1 or len(self.streams) > 1 else 1
         shape = (rps, W) if fmt == "rgba8" else (rps, W, 4)
         dtype = torch.int32 if fmt == "rgba8" else torch.float32
-        if self.plan.weighted:
+        if plan.weighted:
             # shards back to back in the root's gather buffer; the root packs its
             # own rows straight into the head of it
             n = self.nmine
@@ -305,15 +419,15 @@ class DistributedFrame:
             else:
                 self.gathered = None
                 self.wires = [torch.empty((n, 3 * W), dtype=torch.uint8, device=dev) for _ in range(nbuf)]
-        elif self.wire == "rgb8":
-            # render into a local RGBA8 band, pack each chunk into the slot being gathered
-            self.locals = [torch.empty(shape, dtype=dtype, device=dev) for _ in range(nbuf)]
-            self.wires = [torch.empty((rps, 3 * W), dtype=torch.uint8, device=dev) for _ in range(nbuf)]
         else:
-            # the render kernel writes straight into the slot being gathered
-            self.locals = None
-            self.wires = [torch.empty(shape, dtype=dtype, device=dev) for _ in range(nbuf)]
-        if not self.plan.weighted:
+            if self.wire == "rgb8":
+                # render into a local RGBA8 band, pack each chunk into the slot being gathered
+                self.locals = [torch.empty(shape, dtype=dtype, device=dev) for _ in range(nbuf)]
+                self.wires = [torch.empty((rps, 3 * W), dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+            else:
+                # the render kernel writes straight into the slot being gathered
+                self.locals = None
+                self.wires = [torch.empty(shape, dtype=dtype, device=dev) for _ in range(nbuf)]
             wire = self.wires[0]
             self.gathered = ([torch.empty((world,) + tuple(wire.shape), dtype=wire.dtype, device=dev)
                               for _ in range(2)] if rank == 0 and world > 1 else None)
@@ -325,23 +439,18 @@ class DistributedFrame:
         else:
             self.frames = None
         self.frame = self.frames[0] if self.frames is not None else None
-        self.k = 0            # frames submitted
-        self.pending = None   # (slot, stream, [works]) of the frame whose gather is in flight
-        self._pipe = self._pipelined()
+        self._views = {}  # the gathers' tensors and ops, per slot and chunk (_gather_views)
         self._prepare_calls()
 
     def _prepare_calls(self):
         """The per-frame native calls of submit() with their arguments built
-        once per slot and chunk (render, RGB8 pack, the root's de-interleave):
-        the Python wrappers' checks cost as much host time as a rank's frame
-        takes on the GPU at N = 8."""
+        once per slot and chunk (render, RGB8 pack, the root's de-interleave)."""
         import ctypes
 
         import torch
 
         from ._lib import lib
         L, p, ctx = lib(), self.plan, self.r._ctx
-        rgba8 = self.fmt == "rgba8"
 
         def vp(t):
             return ctypes.c_void_p(t.data_ptr())
@@ -356,50 +465,24 @@ class DistributedFrame:
                     rc.append(None)
                     pc.append(None)
                     continue
-                if p.weighted:
-                    fn = L.rm_render_cycle_rows_rgba8 if rgba8 else L.rm_render_cycle_rows
-                    args = (ctx, p.W, p.H, p.cycle, p.offsets[self.rank], p.part_runs[self.rank], j0, j1 - j0,
-                            vp(dst[j0:j1]), None)
-                else:
-                    fn = L.rm_render_rows_rgba8 if rgba8 else L.rm_render_rows
-                    args = (ctx, p.W, p.H, p.band, p.nshards, self.rank, j0, j1 - j0, vp(dst[j0:j1]), None)
-                rc.append((fn, args))
+                rc.append(self._render_call(dst, j0, j1))
                 pc.append((L.rm_pack_rgb8, (ctx, (j1 - j0) * p.W, vp(self.locals[slot][j0:j1]),
                                             vp(self.wires[slot][j0:j1]))) if self.locals is not None else None)
             self._render_calls.append(rc)
             self._pack_calls.append(pc)
             d = None
-            if self.rank == 0 and self.world > 1 and self.gathered is not None:
+            if self.rank == 0 and self.world > 1:
                 g, f = self.gathered[slot], self.frames[slot]
-                if p.weighted:
+                if p.weighted:  # parts back to back
                     n = p.nshards
                     d = (L.rm_deinterleave_cycle_rgb8,
                          (ctx, p.W, p.H, p.cycle, n, (ctypes.c_int * n)(*p.offsets), (ctypes.c_int * n)(*p.part_runs),
                           (ctypes.c_int64 * n)(*[b * 3 * p.W for b in p.part_bases()]), vp(g), vp(f)))
-                elif g.dtype == torch.uint8:
-                    d = (L.rm_deinterleave_rgb8, (ctx, p.W, p.H, p.band, p.nshards, p.rows_per_shard, vp(g), vp(f)))
-                else:
-                    fn = L.rm_deinterleave_rgba8 if rgba8 else L.rm_deinterleave
+                else:  # padded slots
+                    fn = (L.rm_deinterleave_rgb8 if g.dtype == torch.uint8 else
+                          L.rm_deinterleave_rgba8 if self.fmt == "rgba8" else L.rm_deinterleave)
                     d = (fn, (ctx, p.W, p.H, p.band, p.nshards, p.rows_per_shard, vp(g), vp(f)))
             self._deint_calls.append(d)
-
-    def _native(self, call):
-        from ._lib import check
-        rc = call[0](*call[1])
-        if rc:
-            check(rc, self.r._ctx)
-
-    def _pipelined(self):
-        import torch.distributed as dist
-        return self.world > 1 and dist.get_backend(self.group) != "gloo"
-
-    def _render_into(self, dst, j0, j1, stats=False):
-        """Packed rows [j0, j1) of this rank's part into dst[j0:j1]."""
-        p = self.plan
-        if p.weighted:
-            return self.r.render_cycle_rows(p.W, p.H, p.cycle, p.offsets[self.rank], p.part_runs[self.rank], j0,
-                                            j1 - j0, dst[j0:j1], stats=stats)
-        return self.r.render_rows(p.W, p.H, p.band, p.nshards, self.rank, j0, j1 - j0, dst[j0:j1], stats=stats)
 
     def _render_rows(self, c, slot, events=None, st=None):
         """Chunk c of this rank's rows into slot `slot` (and packed to RGB8), on
@@ -409,48 +492,46 @@ class DistributedFrame:
             return
         if events is not None:
             events[0].record(st)
-        self._native(call)
+        self._native(*call)
         if events is not None:
             events[1].record(st)
         if self._pack_calls[slot][c] is not None:
-            self._native(self._pack_calls[slot][c])
+            self._native(*self._pack_calls[slot][c])
 
     def _gather_views(self, slot, c):
         """The tensors of chunk c's gather (c None: every row), cached per slot
         and chunk (slicing them per frame costs host time at N = 8): for
         point-to-point parts the (peer, tensor) pairs, else (send, gather_list)."""
-        key = (slot, c)
-        cache = self.__dict__.setdefault("_views", {})
-        if key in cache:
-            return cache[key]
-        p = self.plan
-        if p.weighted:
-            pairs = []
+        v = self._views.get((slot, c))
+        if v is not None:
+            return v
+
+        def span(q):  # the rows rank q sends
+            cq = self.all_cuts[q]
+            return (0, cq[-1]) if c is None else (cq[c], cq[c + 1])
+
+        j0, j1 = span(self.rank)
+        if self.plan.weighted:
+            v = []
             if self.rank == 0:
-                base = p.part_bases()
+                base = self.plan.part_bases()
                 for q in range(1, self.world):
-                    cq = self.all_cuts[q]
-                    j0, j1 = (0, p.count(q)) if c is None else (cq[c], cq[c + 1])
-                    if j1 > j0:
-                        pairs.append((q, self.gathered[slot][base[q] + j0: base[q] + j1]))
-            else:
-                j0, j1 = (0, self.nmine) if c is None else (self.cuts[c], self.cuts[c + 1])
-                if j1 > j0:
-                    pairs.append((0, self.wires[slot][j0:j1]))
-            v = pairs
+                    k0, k1 = span(q)
+                    if k1 > k0:
+                        v.append((q, self.gathered[slot][base[q] + k0: base[q] + k1]))
+            elif j1 > j0:
+                v.append((0, self.wires[slot][j0:j1]))
         else:
-            j0, j1 = (0, p.rows_per_shard) if c is None else (self.cuts[c], self.cuts[c + 1])
             g = self.gathered[slot] if self.rank == 0 else None
             v = (self.wires[slot][j0:j1], [g[r, j0:j1] for r in range(self.world)] if self.rank == 0 else None)
-        cache[key] = v
+        self._views[(slot, c)] = v
         return v
 
     def _gather_async(self, slot, c):
         """Start chunk c's gather (c None: every row); returns the works."""
         import torch.distributed as dist
-        p = self.plan
         v = self._gather_views(slot, c)
-        if p.weighted:  # point-to-point: the parts differ in size (the ops reused frame after frame)
+        if self.plan.weighted:  # point-to-point: the parts differ in size (the ops reused frame after frame)
             ops = self._views.get(("ops", slot, c))
             if ops is None:
                 op = dist.irecv if self.rank == 0 else dist.isend
@@ -460,68 +541,29 @@ class DistributedFrame:
 
     def _gather_blocking(self, slot):
         """The host-staged gather (gloo), completed inside the call."""
-        if self.plan.weighted:
-            gather_parts_to_root(self.wires[slot], self.plan, self.rank, group=self.group,
-                                 out=self.gathered[slot] if self.rank == 0 else None)
-        else:
-            gather_to_root(self.wires[slot], self.plan, self.rank, group=self.group,
-                           out=self.gathered[slot] if self.rank == 0 else None)
+        gather = gather_parts_to_root if self.plan.weighted else gather_to_root
+        gather(self.wires[slot], self.plan, self.rank, group=self.group,
+               out=self.gathered[slot] if self.rank == 0 else None)
 
-    def _deinterleave(self, slot):
-        p = self.plan
-        if p.weighted:
-            self.r.deinterleave_cycle_rgb8(p.W, p.H, p.cycle, list(p.offsets), list(p.part_runs),
-                                           [b * 3 * p.W for b in p.part_bases()], self.gathered[slot],
-                                           out=self.frames[slot])
-        else:
-            self.r.deinterleave(p.W, p.H, p.band, p.nshards, p.rows_per_shard, self.gathered[slot],
-                                out=self.frames[slot])
-
-    def _bind(self, st):
-        """Bind the renderer to frame stream st.  The frame streams other than
-        the caller's come from PyTorch's pool, which never destroys them, so
-        they are bound as kept (rm_set_stream_kept): leaving one records no
-        marker (DESIGN.md 2.14)."""
-        self.r.set_stream(st, kept=st is not self.caller)
-
-    def render_local(self, stats=False):
-        """This rank's rows only, into slot 0 (no gather), on the first frame
-        stream (whose adaptive tile order the frames use); stats: one
-        synchronous launch.  Ordered before later work on the caller's stream."""
-        import torch
-        dst = self.wires[0] if self.locals is None else self.locals[0]
-        st = self.streams[0]
-        with torch.cuda.stream(st):
-            self._bind(st)
-            try:
-                res = self._render_into(dst, 0, self.nmine, stats=stats)
-            finally:
-                self.r.set_stream(self.caller)
-        if st is not self.caller:
-            self.caller.wait_stream(st)
-        return res
+    def _local_part(self, stats):
+        return self._render_into(self.wires[0] if self.locals is None else self.locals[0], 0, self.nmine, stats=stats)
 
     def submit(self, events=None):
         """Enqueue one frame.  With N > 1 its gather stays in flight until the
         next submit()/flush().  events: optional list of (start, end)
         torch.cuda.Event pairs, one per chunk, recorded around the renders."""
-        import torch
-
         slot = self.k % len(self.wires)
         st = self.streams[self.k % len(self.streams)]
         self.k += 1
-        nch = len(self.cuts) - 1
         works = []
-        with _OnStream(st):  # the collectives order themselves after this stream
-            self._bind(st)
-            for c in range(nch):
+        with _Bound(self, st):  # the collectives order themselves after this stream
+            for c in range(len(self.cuts) - 1):
                 self._render_rows(c, slot, None if events is None else events[c], st)
                 if self._pipe:
                     works.extend(self._gather_async(slot, c))
             if self.world > 1 and not self._pipe:  # gloo: one host-staged gather, completed here
                 self._gather_blocking(slot)
                 works = None
-        self.r.set_stream(self.caller)
         if self.world == 1:
             self.frame = self.frames[slot]
         prev, self.pending = self.pending, (slot, st, works) if self.world > 1 else None
@@ -530,47 +572,15 @@ class DistributedFrame:
         return self.frame
 
     def _complete(self, item):
-        import torch
-
         slot, st, works = item
-        with _OnStream(st):
-            self._bind(st)
+        with _Bound(self, st):
             for w in works or ():
                 w.wait()  # st waits for the gather
             if self.rank == 0:
-                self._native(self._deint_calls[slot])
+                self._native(*self._deint_calls[slot])
                 self.frame = self.frames[slot]
-        self.r.set_stream(self.caller)
-
-    def flush(self):
-        """Finish the frame in flight (rank 0: its de-interleaved frame is in
-        .frame, ordered before later work on the caller's stream)."""
-        import torch
-
-        if self.pending is not None:
-            item, self.pending = self.pending, None
-            self._complete(item)
-        for st in self.streams[1:]:
-            ev = torch.cuda.Event()
-            ev.record(st)
-            self.streams[0].wait_event(ev)
-        if self.streams[0] is not self.caller:  # ... and the caller's stream after them
-            self.caller.wait_stream(self.streams[0])
-        return self.frame
-
-    def render(self, events=None):
-        """One complete frame (submit + flush)."""
-        self.submit(events)
-        return self.flush()
 
     def timed_exchange(self):
-        """(see _timed_exchange); the renderer is back on the caller's stream after it."""
-        try:
-            return self._timed_exchange()
-        finally:
-            self.r.set_stream(self.caller)
-
-    def _timed_exchange(self):
         """One frame with its steps run one after another and each timed alone
         (nothing pipelined): this rank's render, the RGB8 pack, then -- once
         every rank has packed (barrier) -- the gather, and on rank 0 the
@@ -583,16 +593,14 @@ class DistributedFrame:
         import torch
         import torch.distributed as dist
 
-        st, slot = self.streams[0], 0
-        dev = torch.device(f"cuda:{self.r.device}")
+        st, slot, dev = self.streams[0], 0, self.dev
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
         self.flush()
         torch.cuda.synchronize(dev)
-        self._bind(st)
-        with torch.cuda.stream(st):
+        with _Bound(self, st):
             ev[0].record(st)
             if self.nmine:
-                self._render_into(self.wires[slot] if self.locals is None else self.locals[slot], 0, self.nmine)
+                self._local_part(False)
             ev[1].record(st)
             if self.locals is not None and self.nmine:
                 self.r.pack_rgb8(self.locals[slot][: self.nmine], out=self.wires[slot][: self.nmine])
@@ -603,8 +611,8 @@ class DistributedFrame:
         if self.world == 1:
             return out
         dist.barrier(group=self.group)
-        if self._pipelined():
-            with torch.cuda.stream(st):
+        if self._pipe:
+            with _OnStream(st):
                 ev[3].record(st)
                 for w in self._gather_async(slot, None):
                     w.wait()  # st waits for the gather
@@ -617,9 +625,9 @@ class DistributedFrame:
             torch.cuda.synchronize(dev)
             out["gather_ms"] = (time.perf_counter() - t0) * 1e3
         if self.rank == 0:
-            with torch.cuda.stream(st):
+            with _Bound(self, st):
                 ev[4].record(st)
-                self._deinterleave(slot)
+                self._native(*self._deint_calls[slot])
                 ev[5].record(st)
             torch.cuda.synchronize(dev)
             out["deinterleave_ms"] = ev[4].elapsed_time(ev[5])
@@ -627,7 +635,7 @@ class DistributedFrame:
         return out
 
 
-class DeltaFrame(DistributedFrame):
+class DeltaFrame(_ShardedFrame):
     """A row-sharded RGBA8 frame whose parts cross the wire compressed
     (rm_wire_encode: a lossless delta code per 64-pixel row segment, 4-5x
     fewer bytes than RGB8 on rendered frames).  Same plans
@@ -644,30 +652,21 @@ class DeltaFrame(DistributedFrame):
     their frame rows (rm_wire_decode); no de-interleave pass."""
 
     def __init__(self, renderer, W, H, band, rank, world, group=None, chunks=1, streams=None, runs=None):
+        import ctypes
+
         import torch
 
+        from ._lib import lib
+        from .api import wire_capacity, wire_workspace_bytes
         if world < 2:
             raise ValueError("DeltaFrame needs two or more ranks")
         if chunks != 1:
             raise ValueError("DeltaFrame sends whole parts (chunks=1)")
-        self.r, self.rank, self.world, self.fmt, self.group = renderer, rank, world, "rgba8", group
-        self.wire = "delta"
-        self.plan = ShardPlan(W, H, band, world, None if runs is None else tuple(int(x) for x in runs))
-        dev = torch.device(f"cuda:{renderer.device}")
-        self.dev = dev
-        if streams is None:
-            streams = 2 if self._pipelined() else 1
-        if streams not in (1, 2):
-            raise ValueError("streams must be 1 or 2")
-        self.caller = torch.cuda.current_stream(dev)
-        self.streams = [self.caller] if streams == 1 else concurrent_streams(dev, streams)
-        if streams > 1:
-            for st in self.streams:
-                st.wait_stream(self.caller)
+        self.fmt, self.wire = "rgba8", "delta"
+        p = ShardPlan(W, H, band, world, None if runs is None else tuple(int(x) for x in runs))
+        super().__init__(renderer, rank, world, group, p, streams)
+        dev = self.dev
         self.ctrl = torch.cuda.Stream(dev)
-        from .api import wire_capacity, wire_workspace_bytes
-        p = self.plan
-        self.nmine = p.count(rank)
         self.cuts = [0, self.nmine]
         nbuf = 2
         self.locals = [torch.empty((self.nmine, W), dtype=torch.int32, device=dev) for _ in range(nbuf)]
@@ -688,31 +687,15 @@ class DeltaFrame(DistributedFrame):
             self.size_ev = [torch.cuda.Event() for _ in range(nbuf)]
         self.slot_works = [[] for _ in range(nbuf)]
         self.frame = self.frames[0] if self.frames is not None else None
-        self.k = 0
-        self.pending = None
         self.last_sizes = [0] * world
         self.fused = rank != 0  # (the render kernel encodes; scene plugins fall back, _render_message)
-        self._pipe = self._pipelined()
         self._zero_size = torch.zeros(1, dtype=torch.int64, device=dev)
         self._allsz = [torch.zeros(world, dtype=torch.int64, device=dev) for _ in range(nbuf)]
-        # the per-frame native calls with their arguments built once (a frame
-        # at N = 8 is ~0.1 ms: Python-side argument checks per call would cost
-        # as much as the GPU work)
-        import ctypes
-
-        from ._lib import lib
         self._L = lib()
         if rank == 0:
-            # the root's own rows (as _render_into, its arguments built once)
-            vp = ctypes.c_void_p
-            if p.weighted:
-                self._root_render = [(self._L.rm_render_cycle_rows_rgba8,
-                                      (renderer._ctx, W, H, p.cycle, p.offsets[0], p.part_runs[0], 0, self.nmine,
-                                       vp(t.data_ptr()), None)) for t in self.locals]
-            else:
-                self._root_render = [(self._L.rm_render_rows_rgba8,
-                                      (renderer._ctx, W, H, p.band, p.nshards, 0, 0, self.nmine, vp(t.data_ptr()),
-                                       None)) for t in self.locals]
+            # the root's per-frame calls with their arguments built once: its
+            # own rows, and the decode of the others' messages
+            self._root_render = [self._render_call(t, 0, self.nmine) for t in self.locals]
             qs = list(range(1, world))
             self._dec = [((ctypes.c_int * len(qs))(*[p.offsets[q] for q in qs]),
                           (ctypes.c_int * len(qs))(*[p.part_runs[q] for q in qs]),
@@ -720,14 +703,10 @@ class DeltaFrame(DistributedFrame):
                           (ctypes.c_void_p * len(qs))(*[self.recv[s_][q].data_ptr() for q in qs]))
                          for s_ in range(nbuf)]
 
-    def _call(self, rc):
-        from ._lib import check
-        check(rc, self.r._ctx)
-
     def _encode(self, slot):
-        self._call(self._L.rm_wire_encode(self.r._ctx, self.plan.W, self.nmine, self.locals[slot].data_ptr(),
-                                          self.msg[slot].data_ptr(), self.ws[slot].data_ptr(),
-                                          self.size_dev[slot].data_ptr()))
+        self._native(self._L.rm_wire_encode, (self.r._ctx, self.plan.W, self.nmine, self.locals[slot].data_ptr(),
+                                              self.msg[slot].data_ptr(), self.ws[slot].data_ptr(),
+                                              self.size_dev[slot].data_ptr()))
 
     def _render_message(self, slot, stats=False):
         """A non-root rank's part straight into its message: the render
@@ -736,14 +715,14 @@ class DeltaFrame(DistributedFrame):
         import ctypes
 
         from ._lib import RmError, RmStats
-        p, q = self.plan, self.rank
+        p = self.plan
         if self.fused:
             s = RmStats() if stats else None
             try:
-                self._call(self._L.rm_render_cycle_rows_wire(
-                    self.r._ctx, p.W, p.H, p.cycle, p.offsets[q], p.part_runs[q], 0, self.nmine,
-                    self.msg[slot].data_ptr(), self.ws[slot].data_ptr(), self.size_dev[slot].data_ptr(),
-                    ctypes.byref(s) if stats else None))
+                self._native(self._L.rm_render_cycle_rows_wire,
+                             (self.r._ctx, p.W, p.H, *self._part, 0, self.nmine, self.msg[slot].data_ptr(),
+                              self.ws[slot].data_ptr(), self.size_dev[slot].data_ptr(),
+                              ctypes.byref(s) if stats else None))
                 return s.as_dict() if stats else None
             except RmError as e:
                 if "built-in scenes only" not in str(e):
@@ -757,17 +736,17 @@ class DeltaFrame(DistributedFrame):
 
     def _scatter(self, slot):
         p = self.plan
-        self._call(self._L.rm_scatter_part_rgba8(self.r._ctx, p.W, p.H, p.cycle, p.offsets[0], p.part_runs[0],
-                                                 self.nmine, self.locals[slot].data_ptr(),
-                                                 self.frames[slot].data_ptr()))
+        self._native(self._L.rm_scatter_part_rgba8, (self.r._ctx, p.W, p.H, *self._part, self.nmine,
+                                                     self.locals[slot].data_ptr(), self.frames[slot].data_ptr()))
+
+    def _message_size_to_host(self, slot, st):
+        self.size_host[slot].copy_(self.size_dev[slot], non_blocking=True)
+        self.size_ev[slot].record(st)
 
     def _produce(self, slot, st, events=None):
         """Render this rank's rows into slot `slot` on stream st, then (root)
         copy them into the frame or (others) encode them."""
-        import torch
-        p = self.plan
-        with _OnStream(st):
-            self._bind(st)
+        with _Bound(self, st):
             for w in self.slot_works[slot]:  # the slot's previous message has left
                 w.wait()
             self.slot_works[slot] = []
@@ -775,7 +754,7 @@ class DeltaFrame(DistributedFrame):
                 events[0].record()
             if self.rank == 0:
                 if self.nmine:
-                    self._call(self._root_render[slot][0](*self._root_render[slot][1]))
+                    self._native(*self._root_render[slot])
                 if events is not None:
                     events[1].record()
                 self._scatter(slot)
@@ -783,9 +762,7 @@ class DeltaFrame(DistributedFrame):
                 self._render_message(slot)  # (render and encode: one kernel plus the scan and compaction)
                 if events is not None:
                     events[1].record()
-                self.size_host[slot].copy_(self.size_dev[slot], non_blocking=True)
-                self.size_ev[slot].record(st)
-        self.r.set_stream(self.caller)
+                self._message_size_to_host(slot, st)
 
     def _sizes_and_messages(self, slot):
         """The size exchange of the frame in `slot`, then its messages posted
@@ -841,25 +818,24 @@ class DeltaFrame(DistributedFrame):
                 raise RuntimeError(f"DeltaFrame: rank {q} reports a {sizes[q]}-byte message; the receive buffer "
                                    f"holds {cap} (wire capacity)")
 
-    def _decode(self, slot, st):
+    def _decode(self, slot):
         p = self.plan
-        self._call(self._L.rm_wire_decode_parts(self.r._ctx, p.W, p.H, p.cycle, self.world - 1, *self._dec[slot],
-                                                self.frames[slot].data_ptr()))
+        self._native(self._L.rm_wire_decode_parts, (self.r._ctx, p.W, p.H, p.cycle, self.world - 1, *self._dec[slot],
+                                                    self.frames[slot].data_ptr()))
 
-    def _exchange(self, slot, st):
-        """Sizes, messages, and on rank 0 the decodes into its frame on st."""
-        import torch
+    def _complete(self, item):
+        """Sizes, messages, and on rank 0 the decodes into its frame on the
+        frame's stream."""
+        slot, st = item
         sizes, works = self._sizes_and_messages(slot)
         self.last_sizes = sizes
         if self.rank == 0:
-            with _OnStream(st):
-                self._bind(st)
+            with _Bound(self, st):
                 for w in works:
                     w.wait()
-                self._decode(slot, st)
+                self._decode(slot)
                 self.decoded[slot].record(st)
                 self.decoded_recorded[slot] = True
-            self.r.set_stream(self.caller)
             self.frame = self.frames[slot]
         else:
             self.slot_works[slot] = works
@@ -869,48 +845,28 @@ class DeltaFrame(DistributedFrame):
         st = self.streams[self.k % len(self.streams)]
         self.k += 1
         self._produce(slot, st, None if events is None else events[0])
+        if not self._pipe:  # gloo: the exchange completes inside the call
+            self._complete((slot, st))
+            return self.frame
         prev, self.pending = self.pending, (slot, st)
-        if not self._pipe:
-            self.pending = None
-            self._exchange(slot, st)
-        elif prev is not None:
-            self._exchange(*prev)
+        if prev is not None:
+            self._complete(prev)
         return self.frame
 
     def flush(self):
-        import torch
-        if self.pending is not None:
-            item, self.pending = self.pending, None
-            self._exchange(*item)
-        for st in self.streams[1:]:
-            ev = torch.cuda.Event()
-            ev.record(st)
-            self.streams[0].wait_event(ev)
-        if self.streams[0] is not self.caller:
-            self.caller.wait_stream(self.streams[0])
+        super().flush()
         for ws in self.slot_works:  # the caller's stream after every message has left
             for w in ws:
                 w.wait()
         return self.frame
 
-    def render_local(self, stats=False):
-        """This rank's part once (rank 0: its rows; the others: their message,
-        as the frames make it); with stats, (rows or message, rm_stats)."""
-        import torch
-        st = self.streams[0]
-        with torch.cuda.stream(st):
-            self._bind(st)
-            try:
-                if self.rank == 0:
-                    res = self._render_into(self.locals[0], 0, self.nmine, stats=stats)
-                else:
-                    s = self._render_message(0, stats=stats)
-                    res = (self.msg[0], s) if stats else self.msg[0]
-            finally:
-                self.r.set_stream(self.caller)
-        if st is not self.caller:
-            self.caller.wait_stream(st)
-        return res
+    def _local_part(self, stats):
+        """Rank 0: its rows; the others: their message, as the frames make it;
+        with stats, (rows or message, rm_stats)."""
+        if self.rank == 0:
+            return self._render_into(self.locals[0], 0, self.nmine, stats=stats)
+        s = self._render_message(0, stats=stats)
+        return (self.msg[0], s) if stats else self.msg[0]
 
     def timed_exchange(self):
         """render_ms (this rank's rows), pack_ms (encode, or the root's copy
@@ -924,9 +880,7 @@ class DeltaFrame(DistributedFrame):
         torch.cuda.synchronize(self.dev)
         st, slot = self.streams[0], 0
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
-        p = self.plan
-        with torch.cuda.stream(st):
-            self._bind(st)
+        with _Bound(self, st):
             ev[0].record(st)
             if self.rank == 0:
                 if self.nmine:
@@ -937,10 +891,8 @@ class DeltaFrame(DistributedFrame):
                 # render + encode in one kernel (the scan and compaction after it count as the pack)
                 self._render_message(slot)
                 ev[1].record(st)
-                self.size_host[slot].copy_(self.size_dev[slot], non_blocking=True)
-                self.size_ev[slot].record(st)
+                self._message_size_to_host(slot, st)
             ev[2].record(st)
-        self.r.set_stream(self.caller)
         torch.cuda.synchronize(self.dev)
         out = dict(render_ms=ev[0].elapsed_time(ev[1]), pack_ms=ev[1].elapsed_time(ev[2]))
         dist.barrier(group=self.group)
@@ -952,16 +904,16 @@ class DeltaFrame(DistributedFrame):
         out["gather_ms"] = (time.perf_counter() - t0) * 1e3
         out["deinterleave_ms"] = 0.0
         if self.rank == 0:
-            with torch.cuda.stream(st):
-                self._bind(st)
+            with _Bound(self, st):
                 ev[3].record(st)
-                self._decode(slot, st)
+                self._decode(slot)
                 ev[4].record(st)
                 self.decoded[slot].record(st)
                 self.decoded_recorded[slot] = True
-            self.r.set_stream(self.caller)
             torch.cuda.synchronize(self.dev)
             out["deinterleave_ms"] = ev[3].elapsed_time(ev[4])
             self.frame = self.frames[slot]
         out["wire_bytes"] = sizes
         return out
+
+

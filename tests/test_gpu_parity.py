@@ -681,14 +681,61 @@ def test_distributed_frame_two_ranks_on_one_gpu(R, torch_cuda):
     assert np.array_equal(frame, ref)
 
 
-class _FakeWork:
-    def __init__(self, ev=None):
-        self.ev = ev
+class _Work:
+    """A torch.distributed work of the in-process two-rank tests: wait() makes
+    the caller's stream wait for the transfer (`ev`, or the "done" event the
+    receiving side leaves in the `entry` both sides share)."""
+
+    def __init__(self, ev=None, entry=None):
+        self.ev, self.entry = ev, entry
 
     def wait(self):
         import torch
-        if self.ev is not None:
-            torch.cuda.current_stream().wait_event(self.ev)
+        ev = self.ev if self.ev is not None else (self.entry or {}).get("done")
+        if ev is not None:
+            torch.cuda.current_stream().wait_event(ev)
+
+
+_PAIR_W, _PAIR_H, _PAIR_BAND = 96, 70, 8
+
+
+def _pair_as_nccl(cls, R, r1, **kw):
+    """A frame of class `cls` for each of two ranks living in this process
+    (rank 0 on R, rank 1 on r1), made as with the "nccl" backend: the RCCL
+    path (pipelined, two frame streams) is taken at construction."""
+    frs = []
+    for rank, rr in ((0, R), (1, r1)):
+        f = cls.__new__(cls)
+        f._pipelined = lambda: True  # as with the "nccl" backend
+        cls.__init__(f, rr, _PAIR_W, _PAIR_H, _PAIR_BAND, rank, 2, **kw)
+        frs.append(f)
+    return frs
+
+
+def _pair_frames_equal_one_rank(torch, frs, R, r1):
+    """Four poses submitted through both ranks (rank 1 first), pipelined: every
+    frame rank 0 ends up with equals the one-rank rm_render_rgba8 frame."""
+    poses = ["P0", "P1", "P2", "P3"]
+    refs = []
+    for name in poses:
+        setup(R, "T", POSES[name], 128)
+        R.set_params(count_evals=0)
+        refs.append(R.render_rgba8(_PAIR_W, _PAIR_H).cpu().numpy())
+    got = []
+    for i, name in enumerate(poses):
+        for f, rr in ((frs[1], r1), (frs[0], R)):
+            setup(rr, "T", POSES[name], 128)
+            rr.set_params(count_evals=0)
+            f.submit()
+        if i > 0:  # frame i-1 is complete on rank 0 once frame i was submitted
+            torch.cuda.synchronize()
+            got.append(frs[0].frame.cpu().numpy())
+    frs[1].flush()
+    got.append(frs[0].flush().cpu().numpy())
+    torch.cuda.synchronize()
+    assert len(got) == len(refs)
+    for g, ref in zip(got, refs):
+        assert np.array_equal(g, ref)
 
 
 @pytest.mark.parametrize("runs", [None, (13, 8), (3, 8)])
@@ -703,7 +750,6 @@ def test_pipelined_two_stream_frames_in_one_process(R, torch_cuda, runs):
     unpadded point-to-point gather and rm_deinterleave_cycle_rgb8)."""
     torch = torch_cuda
     from raymarching_amd.frame import DistributedFrame
-    W, H, band = 96, 70, 8
     side = torch.cuda.Stream()
     sent = {}
 
@@ -715,7 +761,7 @@ def test_pipelined_two_stream_frames_in_one_process(R, torch_cuda, runs):
             ev.record()  # the caller's (frame) stream
             if fr.rank == 1:
                 sent[(fr.k, c)] = (fr.wires[slot][j0:j1], ev)
-                return [_FakeWork()]
+                return [_Work()]
             src1, ev1 = sent.pop((fr.k, c))
             side.wait_event(ev)
             side.wait_event(ev1)
@@ -729,38 +775,15 @@ def test_pipelined_two_stream_frames_in_one_process(R, torch_cuda, runs):
                     fr.gathered[slot][1, j0:j1].copy_(src1)
             done = torch.cuda.Event()
             done.record(side)
-            return [_FakeWork(done)]
+            return [_Work(done)]
         return gather
 
     r1 = rm.Renderer(0)
-    frs = []
-    for rank, rr in ((0, R), (1, r1)):
-        f = DistributedFrame.__new__(DistributedFrame)
-        f._pipelined = lambda: True  # as with the "nccl" backend
-        DistributedFrame.__init__(f, rr, W, H, band, rank, 2, fmt="rgba8", chunks=2, runs=runs)
+    frs = _pair_as_nccl(DistributedFrame, R, r1, fmt="rgba8", chunks=2, runs=runs)
+    for f in frs:
         f._gather_async = fake_gather(f)
-        frs.append(f)
     assert len(frs[0].streams) == 2 and frs[0].wire == "rgb8"
-    poses = ["P0", "P1", "P2", "P3"]
-    refs = []
-    for name in poses:
-        setup(R, "T", POSES[name], 128)
-        R.set_params(count_evals=0)
-        refs.append(R.render_rgba8(W, H).cpu().numpy())
-    got = []
-    for i, name in enumerate(poses):
-        for f, rr in ((frs[1], r1), (frs[0], R)):
-            setup(rr, "T", POSES[name], 128)
-            rr.set_params(count_evals=0)
-            f.submit()
-        if i > 0:  # frame i-1 is complete on rank 0 once frame i was submitted
-            torch.cuda.synchronize()
-            got.append(frs[0].frame.cpu().numpy())
-    frs[1].flush()
-    got.append(frs[0].flush().cpu().numpy())
-    torch.cuda.synchronize()
-    for g, ref in zip(got, refs):
-        assert np.array_equal(g, ref)
+    _pair_frames_equal_one_rank(torch, frs, R, r1)
     r1.close()
 
 
@@ -930,6 +953,46 @@ def test_weighted_cycle_parts_rebuild_frame(R, torch_cuda, W, H, runs):
         R.render_cycle_rows(W, H, 4, 3, 2, 0, 1, frame[:1])
 
 
+@pytest.mark.parametrize("band,n", [(5, 3), (16, 4)])
+def test_band_rows_are_cyclic_part_rows(R, torch_cuda, band, n):
+    """Round-robin bands are the cyclic part cycle = band * n, offset =
+    band * shard, run = band: rm_render_rows[_rgba8] and
+    rm_render_cycle_rows[_rgba8] write the same rows, bit for bit, for every
+    shard and for a sub-range of one.  40 x 37 with (5, 3): the last cycle is
+    partial and shard 1 ends mid-band; with (16, 4): shard 3 is empty, and
+    both forms return no rows without touching the buffer."""
+    torch = torch_cuda
+    from raymarching_amd.frame import ShardPlan
+    W, H = 40, 37
+    setup(R, "T", POSES["P1"], 128)
+    R.set_params(count_evals=0)
+    frame = {torch.float32: R.render(W, H), torch.int32: R.render_rgba8(W, H)}
+    plan = ShardPlan(W, H, band, n)
+    assert [plan.count(s) for s in range(n)] == {(5, 3): [15, 12, 10], (16, 4): [16, 16, 5, 0]}[band, n]
+
+    def both(s, j0, cnt, dtype):
+        """Packed rows [j0, j0 + cnt) of shard s through the band and the
+        cyclic form, each into a marked buffer with one row to spare."""
+        outs = []
+        for cyclic in (False, True):
+            out = torch.full((cnt + 1, W) + ((4,) if dtype == torch.float32 else ()), -7, dtype=dtype, device="cuda")
+            if cyclic:
+                R.render_cycle_rows(W, H, band * n, band * s, band, j0, cnt, out)
+            else:
+                R.render_rows(W, H, band, n, s, j0, cnt, out)
+            outs.append(out.view(torch.int32))
+        torch.cuda.synchronize()
+        return outs
+
+    for dtype in (torch.float32, torch.int32):
+        marked = torch.full((1,), -7, dtype=dtype).view(torch.int32).item()
+        for s, j0, cnt in [(s, 0, plan.count(s)) for s in range(n)] + [(0, 3, 4)]:
+            a, b = both(s, j0, cnt, dtype)
+            assert torch.equal(a, b), (dtype, s, j0, cnt)
+            assert torch.equal(a[:cnt], frame[dtype][plan.rows(s)[j0: j0 + cnt]].view(torch.int32)), (dtype, s)
+            assert (a[cnt:] == marked).all(), (dtype, s)  # nothing past the rows asked for
+
+
 def _delta_worker(rank, world, port, runs, q):
     import os as _os
 
@@ -990,18 +1053,8 @@ def test_compressed_wire_pipelined_in_one_process(R, torch_cuda, runs):
     stream semantics: every frame of a pose sequence equals rm_render_rgba8's."""
     torch = torch_cuda
     from raymarching_amd.frame import DeltaFrame
-    W, H, band = 96, 70, 8
     side = torch.cuda.Stream()
     queue = []
-
-    class Work:
-        def __init__(self, entry=None, ev=None):
-            self.entry, self.ev = entry, ev
-
-        def wait(self):
-            ev = self.ev if self.ev is not None else (self.entry or {}).get("done")
-            if ev is not None:
-                torch.cuda.current_stream().wait_event(ev)
 
     def fake(fr):
         def exchange(slot):
@@ -1010,7 +1063,7 @@ def test_compressed_wire_pipelined_in_one_process(R, torch_cuda, runs):
                 mine = int(fr.size_host[slot][0])
                 entry = {"msg": fr.msg[slot], "size": mine}
                 queue.append(entry)
-                return [0, mine], [Work(entry)]
+                return [0, mine], [_Work(entry=entry)]
             entry = queue.pop(0)
             if fr.decoded_recorded[slot]:
                 side.wait_event(fr.decoded[slot])
@@ -1019,38 +1072,15 @@ def test_compressed_wire_pipelined_in_one_process(R, torch_cuda, runs):
             done = torch.cuda.Event()
             done.record(side)
             entry["done"] = done
-            return [0, entry["size"]], [Work(ev=done)]
+            return [0, entry["size"]], [_Work(ev=done)]
         return exchange
 
     r1 = rm.Renderer(0)
-    frs = []
-    for rank, rr in ((0, R), (1, r1)):
-        f = DeltaFrame.__new__(DeltaFrame)
-        f._pipelined = lambda: True  # as with the "nccl" backend
-        DeltaFrame.__init__(f, rr, W, H, band, rank, 2, runs=runs)
+    frs = _pair_as_nccl(DeltaFrame, R, r1, runs=runs)
+    for f in frs:
         f._sizes_and_messages = fake(f)
-        frs.append(f)
     assert len(frs[0].streams) == 2
-    poses = ["P0", "P1", "P2", "P3"]
-    refs = []
-    for name in poses:
-        setup(R, "T", POSES[name], 128)
-        R.set_params(count_evals=0)
-        refs.append(R.render_rgba8(W, H).cpu().numpy())
-    got = []
-    for i, name in enumerate(poses):
-        for f, rr in ((frs[1], r1), (frs[0], R)):
-            setup(rr, "T", POSES[name], 128)
-            rr.set_params(count_evals=0)
-            f.submit()
-        if i > 0:
-            torch.cuda.synchronize()
-            got.append(frs[0].frame.cpu().numpy())
-    frs[1].flush()
-    got.append(frs[0].flush().cpu().numpy())
-    torch.cuda.synchronize()
-    for g, ref in zip(got, refs):
-        assert np.array_equal(g, ref)
+    _pair_frames_equal_one_rank(torch, frs, R, r1)
     r1.close()
 
 
@@ -1066,18 +1096,8 @@ def test_compressed_wire_rccl_exchange_code_in_one_process(R, torch_cuda, runs, 
     torch = torch_cuda
     import torch.distributed as dist
     from raymarching_amd.frame import DeltaFrame
-    W, H, band = 96, 70, 8
     side = torch.cuda.Stream()
     gathered, sent = {}, {}
-
-    class Work:
-        def __init__(self, ev=None, entry=None):
-            self.ev, self.entry = ev, entry
-
-        def wait(self):  # the caller's stream waits for the transfer
-            ev = self.ev if self.ev is not None else (self.entry or {}).get("done")
-            if ev is not None:
-                torch.cuda.current_stream().wait_event(ev)
 
     def all_gather_into_tensor(out, inp, group=None):
         # rank 1 (submitted first in each frame) brings its message size, the
@@ -1099,7 +1119,7 @@ def test_compressed_wire_rccl_exchange_code_in_one_process(R, torch_cuda, runs, 
                 ev.record(torch.cuda.current_stream())
                 entry = {"src": o.tensor, "ev": ev}
                 sent["msg"] = entry
-                works.append(Work(entry=entry))  # (the sender's buffer is free once the copy is done)
+                works.append(_Work(entry=entry))  # (the sender's buffer is free once the copy is done)
             else:
                 entry = sent.pop("msg")
                 assert entry["src"].numel() == o.tensor.numel()
@@ -1110,40 +1130,15 @@ def test_compressed_wire_rccl_exchange_code_in_one_process(R, torch_cuda, runs, 
                 done = torch.cuda.Event()
                 done.record(side)
                 entry["done"] = done
-                works.append(Work(ev=done))
+                works.append(_Work(ev=done))
         return works
 
     monkeypatch.setattr(dist, "all_gather_into_tensor", all_gather_into_tensor)
     monkeypatch.setattr(dist, "P2POp", P2POp)
     monkeypatch.setattr(dist, "batch_isend_irecv", batch_isend_irecv)
     r1 = rm.Renderer(0)
-    frs = []
-    for rank, rr in ((0, R), (1, r1)):
-        f = DeltaFrame.__new__(DeltaFrame)
-        f._pipelined = lambda: True  # as with the "nccl" backend
-        DeltaFrame.__init__(f, rr, W, H, band, rank, 2, runs=runs)
-        frs.append(f)
-    poses = ["P0", "P1", "P2", "P3"]
-    refs = []
-    for name in poses:
-        setup(R, "T", POSES[name], 128)
-        R.set_params(count_evals=0)
-        refs.append(R.render_rgba8(W, H).cpu().numpy())
-    got = []
-    for i, name in enumerate(poses):
-        for f, rr in ((frs[1], r1), (frs[0], R)):
-            setup(rr, "T", POSES[name], 128)
-            rr.set_params(count_evals=0)
-            f.submit()
-        if i > 0:
-            torch.cuda.synchronize()
-            got.append(frs[0].frame.cpu().numpy())
-    frs[1].flush()
-    got.append(frs[0].flush().cpu().numpy())
-    torch.cuda.synchronize()
-    assert len(got) == len(refs)
-    for g, ref in zip(got, refs):
-        assert np.array_equal(g, ref)
+    frs = _pair_as_nccl(DeltaFrame, R, r1, runs=runs)
+    _pair_frames_equal_one_rank(torch, frs, R, r1)
     assert frs[0].last_sizes[0] == 0 and frs[0].last_sizes[1] > 0
     r1.close()
 
@@ -1159,18 +1154,8 @@ def test_rgb8_rccl_gather_code_in_one_process(R, torch_cuda, runs, monkeypatch):
     torch = torch_cuda
     import torch.distributed as dist
     from raymarching_amd.frame import DistributedFrame
-    W, H, band = 96, 70, 8
     side = torch.cuda.Stream()
     pending = {}
-
-    class Work:
-        def __init__(self, ev=None, entry=None):
-            self.ev, self.entry = ev, entry
-
-        def wait(self):
-            ev = self.ev if self.ev is not None else (self.entry or {}).get("done")
-            if ev is not None:
-                torch.cuda.current_stream().wait_event(ev)
 
     def copy_after(dst, src, ev):
         side.wait_stream(torch.cuda.current_stream())
@@ -1185,14 +1170,14 @@ def test_rgb8_rccl_gather_code_in_one_process(R, torch_cuda, runs, monkeypatch):
         if gather_list is None:  # rank 1 (submitted first)
             entry = {"src": tensor, "ev": ev}
             pending["gather"] = entry
-            return Work(entry=entry)
+            return _Work(entry=entry)
         entry = pending.pop("gather")
         copy_after(gather_list[0], tensor, ev)
         copy_after(gather_list[1], entry["src"], entry["ev"])
         done = torch.cuda.Event()
         done.record(side)
         entry["done"] = done
-        return Work(ev=done)
+        return _Work(ev=done)
 
     class P2POp:
         def __init__(self, op, tensor, peer, group=None):
@@ -1206,7 +1191,7 @@ def test_rgb8_rccl_gather_code_in_one_process(R, torch_cuda, runs, monkeypatch):
             if o.op is dist.isend:
                 entry = {"src": o.tensor, "ev": ev}
                 pending["p2p"] = entry
-                works.append(Work(entry=entry))
+                works.append(_Work(entry=entry))
             else:
                 entry = pending.pop("p2p")
                 assert entry["src"].numel() == o.tensor.numel()
@@ -1214,40 +1199,15 @@ def test_rgb8_rccl_gather_code_in_one_process(R, torch_cuda, runs, monkeypatch):
                 done = torch.cuda.Event()
                 done.record(side)
                 entry["done"] = done
-                works.append(Work(ev=done))
+                works.append(_Work(ev=done))
         return works
 
     monkeypatch.setattr(dist, "gather", gather)
     monkeypatch.setattr(dist, "P2POp", P2POp)
     monkeypatch.setattr(dist, "batch_isend_irecv", batch_isend_irecv)
     r1 = rm.Renderer(0)
-    frs = []
-    for rank, rr in ((0, R), (1, r1)):
-        f = DistributedFrame.__new__(DistributedFrame)
-        f._pipelined = lambda: True  # as with the "nccl" backend
-        DistributedFrame.__init__(f, rr, W, H, band, rank, 2, fmt="rgba8", runs=runs)
-        frs.append(f)
-    poses = ["P0", "P1", "P2", "P3"]
-    refs = []
-    for name in poses:
-        setup(R, "T", POSES[name], 128)
-        R.set_params(count_evals=0)
-        refs.append(R.render_rgba8(W, H).cpu().numpy())
-    got = []
-    for i, name in enumerate(poses):
-        for f, rr in ((frs[1], r1), (frs[0], R)):
-            setup(rr, "T", POSES[name], 128)
-            rr.set_params(count_evals=0)
-            f.submit()
-        if i > 0:
-            torch.cuda.synchronize()
-            got.append(frs[0].frame.cpu().numpy())
-    frs[1].flush()
-    got.append(frs[0].flush().cpu().numpy())
-    torch.cuda.synchronize()
-    assert len(got) == len(refs)
-    for g, ref in zip(got, refs):
-        assert np.array_equal(g, ref)
+    frs = _pair_as_nccl(DistributedFrame, R, r1, fmt="rgba8", runs=runs)
+    _pair_frames_equal_one_rank(torch, frs, R, r1)
     r1.close()
 
 
