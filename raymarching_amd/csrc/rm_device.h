@@ -67,7 +67,21 @@ struct FrameConst {
     uint32_t* persist;             // KERNEL_PERSIST: {next dispatch ordinal, waves done}, zero between launches
     uint32_t run_magic;            // floor(j / run) = umulhi(j, run_magic) for every packed row j, or 0: divide
     uint32_t gx_magic;             // floor(t / tiles_x) = umulhi(t, gx_magic) for every tile t, or 0: divide
+    float camq_x, camq_y, camq_z;  // sponge_space<false>(u_pos): the primary rays' origin in sponge space (scene T),
+                                   // the same FMAs in the same order on the host (camera_sponge_origin)
 };
+
+// FrameConst.camq_*: sponge_space<false>(F, u_pos) below, FMA for FMA (each one
+// rounding, on the host as on the device), so that scene T's lanes do not each
+// repeat its 9 VALU per pixel
+__host__ inline void camera_sponge_origin(FrameConst& F) {
+    const float x = F.pos_x, y = F.pos_y - 3.0f, z = F.pos_z;
+    const float x1 = __builtin_fmaf(x, F.ry_c, z * F.ry_s);
+    const float z1 = __builtin_fmaf(z, F.ry_c, -(x * F.ry_s));
+    F.camq_x = x1;
+    F.camq_y = __builtin_fmaf(y, F.rx_c, -(z1 * F.rx_s));
+    F.camq_z = __builtin_fmaf(z1, F.rx_c, y * F.rx_s);
+}
 
 // Division by a per-launch divisor d (host: div_magic): with m = floor(2^32 / d)
 // + 1 = (2^32 + e) / d, e in [1, d], a m / 2^32 = a / d + a e / (d 2^32), which
@@ -120,6 +134,21 @@ __device__ __forceinline__ V3 normalize(V3 a) { return a * (1.0f / sqrtf(dot(a, 
 __device__ __forceinline__ float gmin(float x, float y) { return y < x ? y : x; }
 __device__ __forceinline__ float gmax(float x, float y) { return x < y ? y : x; }
 __device__ __forceinline__ float clamp01(float x) { return gmin(gmax(x, 0.0f), 1.0f); }
+// MED3 (scenes S0/T: fog depth, reflection factor, the contrast smoothsteps):
+// the clamp as one v_med3_f32 (which the compiler folds into the clamp modifier
+// of the multiply before it) instead of two compares and two selects.  For a
+// non-NaN x the median of (x, 0, 1) is clamp01(x), except that x = -0 gives +0
+// where clamp01 gives -0; each of these uses squares the result or subtracts
+// it from 1, which ends in the same float.  Their arguments are never NaN in
+// scenes S0/T: a length over a constant, and tonemapped colours whose shading
+// terms are non-negative sums (phong's pow only of dot(R, V) >= 0, the
+// tonemap's log2 of a non-negative number).  Scenes O/OG and plugins keep the
+// GLSL form, in which a NaN colour propagates.
+template <bool MED3>
+__device__ __forceinline__ float clamp01_as(float x) {
+    if constexpr (MED3) return __builtin_amdgcn_fmed3f(x, 0.0f, 1.0f);
+    else return clamp01(x);
+}
 // GLSL mix as the implementation that renders the golden fixtures evaluates it:
 // x + (y - x) a (the spec writes x (1 - a) + y a; bit-exact on 4096 triples,
 // tools/ss_probe.py)
@@ -128,8 +157,9 @@ __device__ __forceinline__ V3 mix3(V3 x, V3 y, float a) {
     return v3(gmix(x.x, y.x, a), gmix(x.y, y.y, a), gmix(x.z, y.z, a));
 }
 __device__ __forceinline__ float fract(float x) { return x - floorf(x); }
+template <bool MED3 = false>
 __device__ __forceinline__ float smoothstep(float e0, float e1, float x) {
-    float t = clamp01((x - e0) / (e1 - e0));
+    float t = clamp01_as<MED3>((x - e0) / (e1 - e0));
     return t * t * (3.0f - 2.0f * t);
 }
 // reflect(I,N) = I - 2*dot(N,I)*N
@@ -559,24 +589,34 @@ __device__ __forceinline__ float vignette(float tcx, float tcy) {
     return 0.5f + 0.5f * gpow<FAST>(16.0f * tcx * tcy * (1.0f - tcx) * (1.0f - tcy), 0.1f);
 }
 // tonemap -> contrast (common.frag:1067) -> vignette (v = vignette(texcoord))
-template <bool FAST>
+// MED3 (scenes S0/T): clamp01_as
+template <bool FAST, bool MED3 = false>
 __device__ __forceinline__ V3 post_colour(V3 c, float v) {
     V3 t = v3(tonemap1<FAST>(c.x, 0.85f), tonemap1<FAST>(c.y, 0.97f), tonemap1<FAST>(c.z, 1.0f));
-    t = v3(smoothstep(0.15f, 1.1f, t.x), smoothstep(0.15f, 1.1f, t.y), smoothstep(0.15f, 1.1f, t.z));
+    t = v3(smoothstep<MED3>(0.15f, 1.1f, t.x), smoothstep<MED3>(0.15f, 1.1f, t.y), smoothstep<MED3>(0.15f, 1.1f, t.z));
     return t * v;
 }
 
 // common.frag:1032-1042 with be = bi = vec3(2) and the fog colour of the scenes
-template <bool FAST = false>
+// TRIM (scenes S0/T): the length as a bare v_sqrt_f32 and the clamp as one
+// v_med3_f32 (clamp01_as).  Without correctly rounded sqrt, sqrtf(x) is
+// v_sqrt_f32 wrapped in a rescaling that acts only for x < 2^-96 (compare,
+// select, ldexp before and after: 5 VALU); here x = |p - ro|^2 >= ZNEAR^2 =
+// 4e-4, p being a march's end point at depth >= ZNEAR (or ro + rd ZFAR), so the
+// bare instruction returns the same float.
+template <bool FAST = false, bool TRIM = false>
 __device__ __forceinline__ V3 apply_scattering(V3 color, V3 ro, V3 p) {
-    float d = 1.0f - clamp01(length(p - ro) / ZFAR);
+    const V3 v = p - ro;
+    const float len = TRIM ? __builtin_amdgcn_sqrtf(dot(v, v)) : length(v);
+    float d = 1.0f - clamp01_as<TRIM>(len / ZFAR);
     float e = FAST ? __builtin_amdgcn_exp2f(d * -2.8853900817779268f) : expf(-d * 2.0f);  // 2 log2(e)
     return color * (1.0f - e) + v3(0.34f, 0.435f, 0.57f) * e;
 }
 // output_shader.frag:178-182
 // (the sky's fog in the colour-only fast form, as every scene's colour path, rm_render_direct.h)
+template <bool TRIM = false>
 __device__ __forceinline__ V3 background(V3 ro, V3 rd) {
-    return apply_scattering<true>(v3s(0.0f), ro, ro + rd * ZFAR);
+    return apply_scattering<true, TRIM>(v3s(0.0f), ro, ro + rd * ZFAR);
 }
 
 // RGBA8 unorm of the reference's RenderTexture: clamp, round to nearest
@@ -587,6 +627,24 @@ __device__ __forceinline__ uint32_t to_unorm8(float c) {
 }
 __device__ __forceinline__ uint32_t pack_rgba8(float r, float g, float b, float a) {
     return to_unorm8(r) | (to_unorm8(g) << 8) | (to_unorm8(b) << 16) | (to_unorm8(a) << 24);
+}
+// The same word from v_cvt_pk_u8_f32, which rounds to nearest even, saturates
+// to [0, 255] (NaN -> 0) and places the byte: a multiply and a convert per
+// channel instead of clamp, multiply, round, convert and the shifts and ORs
+// (the rm_pack_rgba8 pass and the stores of scenes S0/T;
+// tests/test_scene_t_trim.py compares it with to_unorm8's restatement on every
+// k/255 and rounding tie with their neighbours, zeros, denormals, negatives,
+// values up to 1e30, infinities and NaN).  c >= 1 gives c * 255 >= 255 and
+// c <= 0 gives c * 255 <= 0 (the multiply is monotonic), so saturating after
+// the multiply equals clamping before it.
+__device__ __forceinline__ uint32_t pack_unorm8_into(uint32_t word, float c, uint32_t byte) {
+    return __builtin_amdgcn_cvt_pk_u8_f32(c * 255.0f, byte, word);
+}
+__device__ __forceinline__ uint32_t pack_rgba8_sat(float r, float g, float b, float a) {
+    return pack_unorm8_into(pack_unorm8_into(pack_unorm8_into(pack_unorm8_into(0u, r, 0u), g, 1u), b, 2u), a, 3u);
+}
+__device__ __forceinline__ uint32_t pack_rgb8_opaque(float r, float g, float b) {  // alpha 1
+    return pack_unorm8_into(pack_unorm8_into(pack_unorm8_into(0xff000000u, r, 0u), g, 1u), b, 2u);
 }
 
 // ------------------------------------------------------------ hashing

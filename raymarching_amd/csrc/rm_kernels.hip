@@ -38,7 +38,7 @@ __global__ __launch_bounds__(256) void rm_pack_rgba8(const float4* __restrict__ 
                                                        size_t n) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         float4 v = in[i];
-        out[i] = pack_rgba8(v.x, v.y, v.z, v.w);
+        out[i] = pack_rgba8_sat(v.x, v.y, v.z, v.w);  // (the pack scenes S0/T store with: rm_device.h)
     }
 }
 

@@ -679,13 +679,22 @@ __device__ __forceinline__ V3 render_O(const FrameConst& F, V3 ro, V3 rd, Tally&
 template <int NB = 3, int SETTLE = 0, int RSTOP = 0>
 __device__ __forceinline__ V3 render_T(const FrameConst& F, V3 ro, V3 rd, Tally& cnt) {
     constexpr int SC = SCENE_T;
-    V3 p = ro + rd * cast_ray_T<NB>(F, sponge_ray(F, ro, rd), cnt);
+    // ro is the camera, u_pos: its sponge-space image is the frame's, F.camq_* (rm_device.h camera_sponge_origin)
+    float qx = F.camq_x, qy = F.camq_y, qz = F.camq_z;
+    // (in VGPRs, as the lanes' own results were: an SGPR addend makes the march's three FMAs per step the slow
+    // issue form)
+    asm volatile("" : "+v"(qx), "+v"(qy), "+v"(qz));
+    const LinRay prim{v3(qx, qy, qz), sponge_rot<false>(F, rd.x, rd.y, rd.z)};
+    V3 p = ro + rd * cast_ray_T<NB>(F, prim, cnt);
     V3 n = normal_fast<SC, NB>(F, p, cnt);
     // getColorReflect (common.frag:991-1002); its dead nr normal is skipped
     V3 rdir = reflect(rd, n);
     V3 ror = p + rdir * 0.01f;
     V3 pr = ror + rdir * cast_ray_T<NB, RSTOP>(F, sponge_ray(F, ror, rdir), cnt);
-    float c = clamp01(length(pr - p) * (1.0f / 3.0f));
+    // |pr - p| >= 0.01 (the offset of ror; the march adds depth >= ZNEAR along rdir): far above 2^-96, below
+    // which alone sqrtf's rescaling acts, so the bare v_sqrt_f32 is length()'s float (apply_scattering, TRIM)
+    const V3 pd = pr - p;
+    float c = clamp01_as<true>(__builtin_amdgcn_sqrtf(dot(pd, pd)) * (1.0f / 3.0f));
     const V3 lightPos = v3(20.0f, 50.0f, 0.0f);
     V3 Ld = lightPos - p;
     float ld2 = dot(Ld, Ld);
@@ -698,12 +707,20 @@ __device__ __forceinline__ V3 render_T(const FrameConst& F, V3 ro, V3 rd, Tally&
     float ind = clamp01(dot(n, mnormalize<SC>(lightDir * v3(-1.0f, 0.0f, -1.0f))));
     float fre = clamp01(1.0f + dot(n, rd));
     fre = fre * fre;  // pow(x, 2.0)
-    V3 shading =
-        phong<SC>(v3(1.64f, 1.27f, 0.99f), v3(1.0f, 1.0f, 0.0f), 1280.0f, lightDir, p, ro, n) * shadow_pow<SC>(sha);
+    // shadow_pow(1) is (1, 1, 1) exactly (v_log_f32(1) = 0, v_exp_f32(0) = 1), and sha is 1 on every lane that
+    // took no shadow march or whose march met nothing: the log2 and the two exp2 only in waves with a shadowed lane
+    // (the empty asm keeps it a branch: left free, the compiler computes shadow_pow in every wave and selects)
+    V3 spow = v3s(1.0f);
+    if (__builtin_amdgcn_ballot_w64(sha != 1.0f) != 0) {
+        float s = sha;
+        asm volatile("" : "+v"(s));
+        spow = shadow_pow<SC>(s);
+    }
+    V3 shading = phong<SC>(v3(1.64f, 1.27f, 0.99f), v3(1.0f, 1.0f, 0.0f), 1280.0f, lightDir, p, ro, n) * spow;
     shading = shading + v3(0.16f, 0.20f, 0.28f) * sky * occ;
     shading = shading + v3(0.40f, 0.28f, 0.20f) * ind * occ;
     shading = shading + v3s(fre * occ);
-    return apply_scattering<true>(v3s(c) * shading, ro, p);
+    return apply_scattering<true, true>(v3s(c) * shading, ro, p);
 }
 
 // BASELINE config-1 scene S0: castRayD + normal + lambert
@@ -717,7 +734,7 @@ __device__ __forceinline__ V3 render_S0(const FrameConst& F, V3 ro, V3 rd, Tally
         V3 lightDir = mnormalize<SC>(v3(20.0f, 50.0f, 0.0f) - p);
         return v3(0.2f, 0.02f, 0.02f) * (0.1f + clamp01(dot(n, lightDir)));
     }
-    return background(ro, rd);
+    return background<true>(ro, rd);  // (|rd ZFAR|^2 ~ 2500: apply_scattering's TRIM)
 }
 
 // Camera (output_shader.frag:388-404): gl_TexCoord at the pixel centre.
@@ -737,7 +754,16 @@ __device__ __forceinline__ void camera_ray(const FrameConst& F, int x, int y, fl
     const float ux = FAST ? (tcx - 0.5f) * F.res_x * __builtin_amdgcn_rcpf(F.res_y) : (tcx - 0.5f) * F.res_x / F.res_y;
     const float uy = FAST ? (tcy - 0.5f) * F.res_y * __builtin_amdgcn_rcpf(F.res_y) : (tcy - 0.5f) * F.res_y / F.res_y;
     ro = v3(F.pos_x, F.pos_y, F.pos_z);
-    rd = normalize(v3(ux, -uy, -1.0f));
+    if constexpr (FAST) {
+        // normalize() = a * (1 / sqrtf(dot)) compiles to the range-guarded sqrt (apply_scattering, TRIM) and a
+        // reciprocal of the frexp mantissa rescaled by ldexp (5 VALU), which is v_rcp_f32's float for a normal
+        // argument.  dot = ux^2 + uy^2 + 1 lies in [1, 3) for any aspect up to 2:1 (|ux| <= aspect / 2,
+        // |uy| <= 1/2) and stays a normal float for any finite aspect: the bare v_sqrt_f32 and v_rcp_f32.
+        const V3 v = v3(ux, -uy, -1.0f);
+        rd = v * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(dot(v, v)));
+    } else {
+        rd = normalize(v3(ux, -uy, -1.0f));
+    }
     // rd.yz *= rot(-u_mouse.y); rd.xz *= rot(u_mouse.x)  (row vector x mat2(c,-s,s,c))
     float y1 = rd.y * F.cam1_c + rd.z * -F.cam1_s;
     float z1 = rd.y * F.cam1_s + rd.z * F.cam1_c;
@@ -755,7 +781,8 @@ __device__ __forceinline__ void camera_ray(const FrameConst& F, int x, int y, fl
 // reads unorm8 texels, b * RN(1/255) (within 1 ulp of b / 255).  A part >= 1
 // (the first frame of a still camera) stores the colour: the target needs no
 // clearing.
-template <typename OUT>
+// SAT (scenes S0/T): the RGBA8 word from the saturating packed converts (rm_device.h pack_rgb8_opaque).
+template <bool SAT = false, typename OUT>
 __device__ __forceinline__ void store_pixel(const FrameConst& F, OUT* __restrict__ out, size_t i, V3 c) {
 #pragma clang fp contract(off)
     if (F.accumulate && F.sample_part < 1.0f) {
@@ -771,7 +798,7 @@ __device__ __forceinline__ void store_pixel(const FrameConst& F, OUT* __restrict
         const float a = F.sample_part;
         c = v3(prev.x + (c.x - prev.x) * a, prev.y + (c.y - prev.y) * a, prev.z + (c.z - prev.z) * a);
     }
-    if constexpr (sizeof(OUT) == 4) out[i] = pack_rgba8(c.x, c.y, c.z, 1.0f);
+    if constexpr (sizeof(OUT) == 4) out[i] = SAT ? pack_rgb8_opaque(c.x, c.y, c.z) : pack_rgba8(c.x, c.y, c.z, 1.0f);
     else out[i] = make_float4(c.x, c.y, c.z, 1.0f);
 }
 
@@ -879,9 +906,10 @@ __device__ __forceinline__ void render_tile_at(const FrameConst& F, OUT* __restr
             (void)lat;
             c = render_pixel<SC, 3, kPlaneSpans<SC> ? (COUNT ? 2 : 1) : 0>(F, ro, rd, cnt);
         }
-        c = post_colour<FastColour<SC>::value>(c, vig);
-        if constexpr (kWire) wire_px = pack_rgba8(c.x, c.y, c.z, 1.0f);
-        else store_pixel(F, out, (size_t)j * F.W + x, c);
+        constexpr bool kTrim = FastMath<SC>::value;  // scenes S0/T: one-instruction clamps, saturating pack
+        c = post_colour<FastColour<SC>::value, kTrim>(c, vig);
+        if constexpr (kWire) wire_px = kTrim ? pack_rgb8_opaque(c.x, c.y, c.z) : pack_rgba8(c.x, c.y, c.z, 1.0f);
+        else store_pixel<kTrim>(F, out, (size_t)j * F.W + x, c);
     }
     if constexpr (kWire)
         wire_encode_tile(wire_px, reinterpret_cast<WireTile*>(out), (long long)gx * ((F.nrows + 7) / 8),

@@ -117,6 +117,7 @@ FrameConst frame_const(const rm_ctx *c, int W, int H, const RowPart &part, int n
     float ay = -rot_y * 0.017453292519943295f, ax = -rot_x * 0.017453292519943295f;
     F.ry_c = rm::glsl_cos(ay); F.ry_s = rm::glsl_sin(ay);
     F.rx_c = rm::glsl_cos(ax); F.rx_s = rm::glsl_sin(ax);
+    rm::camera_sponge_origin(F);  // (after pos and the sponge rotation)
     F.W = W; F.H = H;
     F.cycle = part.cycle; F.offset = part.offset; F.run = part.run; F.nrows = nrows;
     F.run_magic = rm::div_magic((uint32_t)part.run, (uint64_t)H + 1);  // packed rows j < H
