@@ -109,6 +109,48 @@ __device__ __forceinline__ int sched_bucket(uint32_t cost) {
 template <int SC>
 struct PluginScene;
 
+// What the render code of a scene may do beyond the GLSL's own arithmetic:
+// every scene-dependent choice below and in rm_render_direct.h is one of these
+// members, named at the call.
+//
+// Every scene (no member: there is no other form): colour-only arithmetic
+// (Phong's normalizations and pow, the shadow factor's pow, the SSS term's pow,
+// fog, tonemap, vignette, the refraction's absorption) uses the hardware
+// exp2/log2/rsq/rcp forms (1-2 ulp).  Nothing that positions a ray or feeds the
+// thickness hash changes by them (marches, normals, the light direction and
+// distance, the floor pattern keep their exact forms), so ray-step counts are
+// untouched and pixels move by ~1e-6.
+template <int SC>
+struct ScenePolicy {
+    // Scenes S0 and T use GLSL-precision hardware ops (v_rcp/v_sqrt/v_rsq, as
+    // GPU GLSL compilers emit them) in marches, normals and the camera as well;
+    // scene O, OG and plugins keep the exact forms there (kExactMarch) because
+    // their normal hash amplifies ulp differences.
+    static constexpr bool kHwMath = SC == SCENE_S0 || SC == SCENE_T;
+    static constexpr bool kExactMarch = !kHwMath;
+    // Scenes S0/T: one-instruction clamps (clamp01_as), the bare v_sqrt_f32 of
+    // apply_scattering and the saturating RGBA8 pack (pack_rgb8_opaque); their
+    // parity arguments are stated at those functions.
+    static constexpr bool kTrim = kHwMath;
+    // Scenes O/OG: the floor-plane spans (plane_probes, rm_render_direct.h),
+    // probe points and probe-form lengths formed with fused multiply-adds (fma3,
+    // len3's FUSE_O), and soft-shadow marches that leave by scene O's settle
+    // rule (shadow_settled_O).
+    static constexpr bool kPlaneSpans = SC == SCENE_O || SC == SCENE_OG;
+    static constexpr bool kProbeFma = kPlaneSpans;
+    static constexpr bool kSettleO = kPlaneSpans;
+    // Minimum waves per SIMD the register allocator must allow.  Scene O asks
+    // for 8 (64 VGPRs): its kernel needs ~82, and the few spills to scratch cost
+    // less than occupancy 5 does (C5 frame 12.29 -> 11.56 ms,
+    // profiles/r02/scene_O_occupancy_ab.jsonl); S0/T fit 8 waves unasked; the
+    // glass test scene OG would spill ~80 VGPRs and keeps its allocation.
+    static constexpr int kWavesPerEU = SC == SCENE_O ? 8 : 1;
+};
+// The two forms of a scene distance (the EXACT parameter of the functions
+// below): the exact form keeps the GLSL's roundings, the probe form serves the
+// AO / shadow / thickness probes, whose results are smooth in the distance.
+constexpr bool kExactForm = true, kProbeForm = false;
+
 // ------------------------------------------------------------- vec3 helpers
 struct V3 {
     float x, y, z;
@@ -157,7 +199,7 @@ __device__ __forceinline__ V3 mix3(V3 x, V3 y, float a) {
     return v3(gmix(x.x, y.x, a), gmix(x.y, y.y, a), gmix(x.z, y.z, a));
 }
 __device__ __forceinline__ float fract(float x) { return x - floorf(x); }
-template <bool MED3 = false>
+template <bool MED3>
 __device__ __forceinline__ float smoothstep(float e0, float e1, float x) {
     float t = clamp01_as<MED3>((x - e0) / (e1 - e0));
     return t * t * (3.0f - 2.0f * t);
@@ -331,7 +373,7 @@ struct LinRay {
     V3 o, d;
 };
 __device__ __forceinline__ LinRay sponge_ray(const FrameConst& F, V3 ro, V3 rd) {
-    return LinRay{sponge_space<false>(F, ro), sponge_rot<false>(F, rd.x, rd.y, rd.z)};
+    return LinRay{sponge_space<kProbeForm>(F, ro), sponge_rot<kProbeForm>(F, rd.x, rd.y, rd.z)};
 }
 __device__ __forceinline__ V3 at(const LinRay& r, float t) {
     return v3(fmaf(r.d.x, t, r.o.x), fmaf(r.d.y, t, r.o.y), fmaf(r.d.z, t, r.o.z));
@@ -345,7 +387,7 @@ __device__ __forceinline__ float menger_at(const LinRay& r, float t, Tally& n, b
         n.evals++;
         n.flop += FL_LINRAY + FL_BOX;
     }
-    return menger<false, NB>(at(r, t), n.flop, active);
+    return menger<ScenePolicy<SCENE_T>::kExactMarch, NB>(at(r, t), n.flop, active);
 }
 
 // sminCubic distance part (common.frag:72-80), k = vec2(k), k > 1e-4.
@@ -364,7 +406,7 @@ __device__ __forceinline__ float smin_cubic_d(float a, float b, float k, float& 
         return fmaf(-(x * x), x * (1.0f / (6.0f * k * k)), __builtin_elementwise_minimum(a, b));
     }
     float x = fmaxf(k - fabsf(a - b), 0.0f);
-    float h = EXACT ? div_const(x, k, 1.0f / k) : x * (1.0f / k);
+    float h = div_const(x, k, 1.0f / k);
     m = h * h * h * 0.5f;
     float s = m * k * (1.0f / 3.0f);
     return __builtin_elementwise_minimum(a, b) - s;
@@ -373,7 +415,7 @@ __device__ __forceinline__ float smin_cubic_d(float a, float b, float k, float& 
 // FUSE_O: scene O's probe form (its sphere and cube distances, !EXACT) fuses
 // the sum of squares (as its probe points, rm_render_direct.h); every other caller
 // (scene S0's sphere) keeps the unfused form
-template <bool EXACT, bool FUSE_O = false>
+template <bool EXACT, bool FUSE_O>
 __device__ __forceinline__ float len3(float x, float y, float z) {
     if constexpr (!EXACT && FUSE_O) return __builtin_amdgcn_sqrtf(fmaf(z, z, fmaf(y, y, x * x)));
     float l2 = x * x + y * y + z * z;
@@ -384,7 +426,8 @@ __device__ __forceinline__ float len3(float x, float y, float z) {
 template <bool EXACT>
 __device__ __forceinline__ float cube(V3 p, V3 c, float r) {
     float qx = fabsf(p.x - c.x) - r, qy = fabsf(p.y - c.y) - r, qz = fabsf(p.z - c.z) - r;
-    return len3<EXACT, true>(fmaxf(qx, 0.0f), fmaxf(qy, 0.0f), fmaxf(qz, 0.0f)) + fminf(fmaxf(qx, fmaxf(qy, qz)), 0.0f);
+    return len3<EXACT, ScenePolicy<SCENE_O>::kProbeFma>(fmaxf(qx, 0.0f), fmaxf(qy, 0.0f), fmaxf(qz, 0.0f)) +
+           fminf(fmaxf(qx, fmaxf(qy, qz)), 0.0f);
 }
 
 // scene O's sceneSDF distance (output_shader.frag:38-48) at world point p with
@@ -435,7 +478,7 @@ __device__ __forceinline__ float scene_dist_O(V3 p, V3 q, Tally& n, float& slack
         if (d0 + 0.34f <= A) return d0;
     }
     n.flop += FL_SPHERE + FL_CUBE + 2 * FL_SMIN;
-    const float d1 = len3<EXACT, true>(p.x - 3.0f, p.y - 2.0f, p.z - 3.0f) - 1.0f;
+    const float d1 = len3<EXACT, ScenePolicy<SCENE_O>::kProbeFma>(p.x - 3.0f, p.y - 2.0f, p.z - 3.0f) - 1.0f;
     const float d2 = cube<EXACT>(p, v3(-5.0f, 4.0f, 5.0f), 1.0f);
     const float t1 = smin_cubic_d<EXACT>(d1, d2, 0.5f, m);
     const float t2 = smin_cubic_d<EXACT>(t1, d3, 0.5f, m);
@@ -461,7 +504,7 @@ __device__ __forceinline__ float scene_dist(const FrameConst& F, V3 p, Tally& n)
     if constexpr (SC == SCENE_S0) {
         n.evals++;
         n.flop += FL_SPHERE;
-        return len3<EXACT>(p.x, p.y - 1.0f, p.z + 3.0f) - 1.0f;  // sphere(vec4(0,1,-3,1), p)
+        return len3<EXACT, ScenePolicy<SC>::kProbeFma>(p.x, p.y - 1.0f, p.z + 3.0f) - 1.0f;  // sphere(vec4(0,1,-3,1), p)
     } else if constexpr (SC == SCENE_T) {
         n.evals++;
         n.flop += FL_TRANSFORM + FL_BOX;
@@ -493,22 +536,15 @@ struct Mat {
           emission(em) {}
 };
 
-
-__device__ __forceinline__ Mat mat_make(V3 d, V3 s, float sh, float refl, float tr, V3 ab, float ior, V3 em) {
-    Mat m;
-    m.diffuse = d; m.specular = s; m.shininess = sh; m.reflectivity = refl; m.transparency = tr;
-    m.absorption = ab; m.refraction_index = ior; m.emission = em;
-    return m;
-}
 __device__ __forceinline__ Mat mat_red() {  // output_shader.frag:12
-    return mat_make(v3(0.2f, 0.02f, 0.02f), v3(0.04f, 0.02f, 0.02f), 32.0f, 0.0f, 0.0f, v3s(0.0f), 1.0f, v3s(0.0f));
+    return Mat(v3(0.2f, 0.02f, 0.02f), v3(0.04f, 0.02f, 0.02f), 32.0f, 0.0f, 0.0f, v3s(0.0f), 1.0f, v3s(0.0f));
 }
 __device__ __forceinline__ Mat mat_blue(bool glass) {  // output_shader.frag:14 (glass: test scene OG)
-    return mat_make(v3(0.02f, 0.02f, 0.2f), v3(0.02f, 0.02f, 0.04f), 32.0f, 0.0f, glass ? 0.9f : 0.0f,
-                    v3(2.0f, 2.0f, 0.75f) * 0.2f, 1.52f, v3(0.0f, 0.0f, 100.0f));
+    return Mat(v3(0.02f, 0.02f, 0.2f), v3(0.02f, 0.02f, 0.04f), 32.0f, 0.0f, glass ? 0.9f : 0.0f,
+               v3(2.0f, 2.0f, 0.75f) * 0.2f, 1.52f, v3(0.0f, 0.0f, 100.0f));
 }
 __device__ __forceinline__ Mat mat_mirror() {  // output_shader.frag:15
-    return mat_make(v3s(0.1f), v3s(0.09f), 64.0f, 0.25f, 0.0f, v3s(0.0f), 1.0f, v3s(0.0f));
+    return Mat(v3s(0.1f), v3s(0.09f), 64.0f, 0.25f, 0.0f, v3s(0.0f), 1.0f, v3s(0.0f));
 }
 // output_shader.frag:16-28
 // (colour only: the blur width and the divisions by it in the hardware
@@ -518,17 +554,18 @@ __device__ __forceinline__ Mat floor_mat(V3 pos) {
     const float l2 = dot(pos, pos);
     const float scale = fmaxf(10.0f, __builtin_amdgcn_exp2f(0.65f * __builtin_amdgcn_logf(l2)));  // |pos|^1.3
     const float is = __builtin_amdgcn_rcpf(scale);
-    float tx = smoothstep(-0.005f, 0.005f, glsl_sin(pos.x * PI_REF) * is);
-    float ty = smoothstep(-0.005f, 0.005f, glsl_sin(pos.z * PI_REF) * is);
+    float tx = smoothstep<ScenePolicy<SCENE_O>::kTrim>(-0.005f, 0.005f, glsl_sin(pos.x * PI_REF) * is);
+    float ty = smoothstep<ScenePolicy<SCENE_O>::kTrim>(-0.005f, 0.005f, glsl_sin(pos.z * PI_REF) * is);
     float tile = fminf(fmaxf(tx, ty), fmaxf(1.0f - tx, 1.0f - ty));
     V3 color = mix3(v3s(0.3f), v3s(0.025f), tile);
-    return mat_make(color, v3s(0.03f), 128.0f, 0.0f, 0.0f, v3s(0.0f), 1.0f, v3s(0.0f));
+    return Mat(color, v3s(0.03f), 128.0f, 0.0f, 0.0f, v3s(0.0f), 1.0f, v3s(0.0f));
 }
 // blendMaterial with ALLOW_MATERIAL_BLENDING (common.frag:37-53)
 __device__ __forceinline__ Mat blend(const Mat& a, const Mat& b, float k) {
-    return mat_make(mix3(a.diffuse, b.diffuse, k), mix3(a.specular, b.specular, k), gmix(a.shininess, b.shininess, k),
-                    gmix(a.reflectivity, b.reflectivity, k), gmix(a.transparency, b.transparency, k),
-                    mix3(a.absorption, b.absorption, k), gmix(a.refraction_index, b.refraction_index, k), mix3(a.emission, b.emission, k));
+    return Mat(mix3(a.diffuse, b.diffuse, k), mix3(a.specular, b.specular, k), gmix(a.shininess, b.shininess, k),
+               gmix(a.reflectivity, b.reflectivity, k), gmix(a.transparency, b.transparency, k),
+               mix3(a.absorption, b.absorption, k), gmix(a.refraction_index, b.refraction_index, k),
+               mix3(a.emission, b.emission, k));
 }
 __device__ __forceinline__ Mat smin_mat(float a, const Mat& ma, float b, const Mat& mb, float m) {
     return blend(ma, mb, a < b ? m : 1.0f - m);
@@ -540,17 +577,17 @@ __device__ __forceinline__ Mat scene_mat(const FrameConst& F, V3 p) {
     if constexpr (SC == SCENE_O || SC == SCENE_OG) {
         constexpr bool glass = SC == SCENE_OG;
         uint32_t fl = 0;  // (the material evaluation is not a ray-step)
-        float d0 = menger<true>(sponge_space<true>(F, p), fl);
-        float d1 = len3<true>(p.x - 3.0f, p.y - 2.0f, p.z - 3.0f) - 1.0f;
-        float d2 = cube<true>(p, v3(-5.0f, 4.0f, 5.0f), 1.0f);
+        float d0 = menger<kExactForm>(sponge_space<kExactForm>(F, p), fl);
+        float d1 = len3<kExactForm, ScenePolicy<SC>::kProbeFma>(p.x - 3.0f, p.y - 2.0f, p.z - 3.0f) - 1.0f;
+        float d2 = cube<kExactForm>(p, v3(-5.0f, 4.0f, 5.0f), 1.0f);
         float d3 = p.y;
         float m1, m2, m3;
-        float t1 = smin_cubic_d<true>(d1, d2, 0.5f, m1);
+        float t1 = smin_cubic_d<kExactForm>(d1, d2, 0.5f, m1);
         Mat b = mat_blue(glass);
         Mat mt1 = smin_mat(d1, b, d2, b, m1);
-        float t2 = smin_cubic_d<true>(t1, d3, 0.5f, m2);
+        float t2 = smin_cubic_d<kExactForm>(t1, d3, 0.5f, m2);
         Mat mt2 = smin_mat(t1, mt1, d3, floor_mat(p), m2);
-        (void)smin_cubic_d<true>(d0, t2, 0.33f, m3);
+        (void)smin_cubic_d<kExactForm>(d0, t2, 0.33f, m3);
         return smin_mat(d0, mat_mirror(), t2, mt2, m3);
     } else if constexpr (SC == SCENE_PLUGIN) {
         return PluginScene<SC>::mat(p);
@@ -562,37 +599,27 @@ __device__ __forceinline__ Mat scene_mat(const FrameConst& F, V3 p) {
 
 // ---------------------------------------------------------- post-colour
 
-// common.frag:1044-1051
-template <bool FAST>
-__device__ __forceinline__ float gpow(float x, float y) {
-    if constexpr (FAST) return __builtin_amdgcn_exp2f(y * __builtin_amdgcn_logf(x));
-    else return powf(x, y);
-}
-// FAST (scenes S0/T): the colour path's division and exp as
-// the hardware reciprocal and exp2 (1 ulp; the colour is smooth in them):
-// arcp division had compiled to a frexp/ldexp-scaled reciprocal, 8 VALU each
-template <bool FAST>
+// common.frag:1044-1051 (colour only: pow as exp2(y log2 x), ScenePolicy)
+__device__ __forceinline__ float gpow(float x, float y) { return __builtin_amdgcn_exp2f(y * __builtin_amdgcn_logf(x)); }
+// The colour path's division and exp as the hardware reciprocal and exp2
+// (1 ulp; the colour is smooth in them): arcp division had compiled to a
+// frexp/ldexp-scaled reciprocal, 8 VALU each
 __device__ __forceinline__ float tonemap1(float c, float e2) {
-    float col = FAST ? (c * 2.0f) * __builtin_amdgcn_rcpf(1.0f + c) : c * 2.0f / (1.0f + c);
-    if constexpr (FAST) {  // pow(pow(x, .4545), e2) = exp2(.4545 e2 log2 x): one log2, one exp2
-        col = __builtin_amdgcn_exp2f((0.4545f * e2) * __builtin_amdgcn_logf(col));
-    } else {
-        col = gpow<FAST>(col, 0.4545f);
-        col = gpow<FAST>(col, e2);
-    }
+    float col = (c * 2.0f) * __builtin_amdgcn_rcpf(1.0f + c);
+    // pow(pow(x, .4545), e2) = exp2(.4545 e2 log2 x): one log2, one exp2
+    col = __builtin_amdgcn_exp2f((0.4545f * e2) * __builtin_amdgcn_logf(col));
     return col * 0.5f + 0.5f * col * col * (3.0f - 2.0f * col);
 }
 // vignette(.., 0.1)'s factor (common.frag:1072): computed before the render, so
 // one value instead of the two texture coordinates stays live through it
-template <bool FAST>
 __device__ __forceinline__ float vignette(float tcx, float tcy) {
-    return 0.5f + 0.5f * gpow<FAST>(16.0f * tcx * tcy * (1.0f - tcx) * (1.0f - tcy), 0.1f);
+    return 0.5f + 0.5f * gpow(16.0f * tcx * tcy * (1.0f - tcx) * (1.0f - tcy), 0.1f);
 }
 // tonemap -> contrast (common.frag:1067) -> vignette (v = vignette(texcoord))
 // MED3 (scenes S0/T): clamp01_as
-template <bool FAST, bool MED3 = false>
+template <bool MED3>
 __device__ __forceinline__ V3 post_colour(V3 c, float v) {
-    V3 t = v3(tonemap1<FAST>(c.x, 0.85f), tonemap1<FAST>(c.y, 0.97f), tonemap1<FAST>(c.z, 1.0f));
+    V3 t = v3(tonemap1(c.x, 0.85f), tonemap1(c.y, 0.97f), tonemap1(c.z, 1.0f));
     t = v3(smoothstep<MED3>(0.15f, 1.1f, t.x), smoothstep<MED3>(0.15f, 1.1f, t.y), smoothstep<MED3>(0.15f, 1.1f, t.z));
     return t * v;
 }
@@ -604,19 +631,18 @@ __device__ __forceinline__ V3 post_colour(V3 c, float v) {
 // select, ldexp before and after: 5 VALU); here x = |p - ro|^2 >= ZNEAR^2 =
 // 4e-4, p being a march's end point at depth >= ZNEAR (or ro + rd ZFAR), so the
 // bare instruction returns the same float.
-template <bool FAST = false, bool TRIM = false>
+template <bool TRIM>
 __device__ __forceinline__ V3 apply_scattering(V3 color, V3 ro, V3 p) {
     const V3 v = p - ro;
     const float len = TRIM ? __builtin_amdgcn_sqrtf(dot(v, v)) : length(v);
     float d = 1.0f - clamp01_as<TRIM>(len / ZFAR);
-    float e = FAST ? __builtin_amdgcn_exp2f(d * -2.8853900817779268f) : expf(-d * 2.0f);  // 2 log2(e)
+    float e = __builtin_amdgcn_exp2f(d * -2.8853900817779268f);  // exp(-2 d): 2 log2(e) (colour only, ScenePolicy)
     return color * (1.0f - e) + v3(0.34f, 0.435f, 0.57f) * e;
 }
 // output_shader.frag:178-182
-// (the sky's fog in the colour-only fast form, as every scene's colour path, rm_render_direct.h)
-template <bool TRIM = false>
+template <bool TRIM>
 __device__ __forceinline__ V3 background(V3 ro, V3 rd) {
-    return apply_scattering<true, TRIM>(v3s(0.0f), ro, ro + rd * ZFAR);
+    return apply_scattering<TRIM>(v3s(0.0f), ro, ro + rd * ZFAR);
 }
 
 // RGBA8 unorm of the reference's RenderTexture: clamp, round to nearest

@@ -75,22 +75,24 @@ __global__ __launch_bounds__(256) void rm_deinterleave_rgb8(const uint8_t* __res
                                                               int nshards, int rows_per_shard, int vec) {
     const int per_row = vec ? W / 4 : W;
     for (int y = blockIdx.y; y < H; y += gridDim.y) {
-    const int gb = y / band, r = y - gb * band;
-    const int shard = gb % nshards, lb = gb / nshards;
-    const uint8_t* src = gathered + ((size_t)shard * rows_per_shard + lb * band + r) * 3 * (size_t)W;
-    uint32_t* dst = out + (size_t)y * W;
-    for (int xg = blockIdx.x * blockDim.x + threadIdx.x; xg < per_row; xg += gridDim.x * blockDim.x) {
-        if (vec) {
-            const uint32_t* s = reinterpret_cast<const uint32_t*>(src) + 3 * xg;
-            const uint32_t w0 = s[0], w1 = s[1], w2 = s[2];
-            reinterpret_cast<uint4*>(dst)[xg] =
-                make_uint4((w0 & 0xFFFFFFu) | 0xFF000000u, (w0 >> 24) | ((w1 & 0xFFFFu) << 8) | 0xFF000000u,
-                           (w1 >> 16) | ((w2 & 0xFFu) << 16) | 0xFF000000u, (w2 >> 8) | 0xFF000000u);
-        } else {
-            const uint8_t* q = src + 3 * (size_t)xg;
-            dst[xg] = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | 0xFF000000u;
+        const int gb = y / band, r = y - gb * band;
+        const int shard = gb % nshards, lb = gb / nshards;
+        const uint8_t* src = gathered + ((size_t)shard * rows_per_shard + lb * band + r) * 3 * (size_t)W;
+        uint32_t* dst = out + (size_t)y * W;
+        // (this row loop is rm_deinterleave_cycle_rgb8's, restated: as a shared function it compiled to other
+        // code, whichever side read blockDim; change them together)
+        for (int xg = blockIdx.x * blockDim.x + threadIdx.x; xg < per_row; xg += gridDim.x * blockDim.x) {
+            if (vec) {
+                const uint32_t* s = reinterpret_cast<const uint32_t*>(src) + 3 * xg;
+                const uint32_t w0 = s[0], w1 = s[1], w2 = s[2];
+                reinterpret_cast<uint4*>(dst)[xg] =
+                    make_uint4((w0 & 0xFFFFFFu) | 0xFF000000u, (w0 >> 24) | ((w1 & 0xFFFFu) << 8) | 0xFF000000u,
+                               (w1 >> 16) | ((w2 & 0xFFu) << 16) | 0xFF000000u, (w2 >> 8) | 0xFF000000u);
+            } else {
+                const uint8_t* q = src + 3 * (size_t)xg;
+                dst[xg] = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | 0xFF000000u;
+            }
         }
-    }
     }
 }
 

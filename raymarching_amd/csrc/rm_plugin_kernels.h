@@ -27,10 +27,11 @@ namespace rm {
 template <bool COUNT>
 __device__ __forceinline__ void plugin_render_tile(const FrameConst& F, void* out, int rgba8,
                                                    unsigned long long* evals) {
+    using P = ScenePolicy<SCENE_PLUGIN>;
     const uint64_t t_start = F.tile_cost ? clock64() : 0;
     const int lane = threadIdx.x;
     int bx = blockIdx.x, by = blockIdx.y;
-    if (F.tile_order) {  // costliest tiles first (rm_params.schedule, rm_set_tile_order)
+    if (F.tile_order) {  // costliest tiles first (rm_params.schedule, rm_set_tile_order; as render_tile_at)
         const uint32_t t = F.tile_order[by * gridDim.x + bx];
         by = div_by((int)t, F.gx_magic, (int)gridDim.x);
         bx = (int)t - by * (int)gridDim.x;
@@ -41,30 +42,19 @@ __device__ __forceinline__ void plugin_render_tile(const FrameConst& F, void* ou
         const int y = shard_row(F, F.row0 + j);
         float tcx, tcy;
         V3 ro, rd;
-        camera_ray<false>(F, x, y, tcx, tcy, ro, rd);
-        const float vig = vignette<FastColour<SCENE_PLUGIN>::value>(tcx, tcy);
+        camera_ray<P::kHwMath>(F, x, y, tcx, tcy, ro, rd);
+        const float vig = vignette(tcx, tcy);
         // the exact skips of scene O's pipeline that hold for any scene (the soft
         // shadows of points facing away from the light): taken
         // by the timed launches, counted by the instrumented ones
         V3 c = render_pixel<SCENE_PLUGIN, 3, COUNT ? 2 : 1>(F, ro, rd, cnt);
-        c = post_colour<FastColour<SCENE_PLUGIN>::value>(c, vig);
+        c = post_colour<P::kTrim>(c, vig);
         const size_t i = (size_t)j * F.W + x;
-        if (rgba8) store_pixel(F, static_cast<uint32_t*>(out), i, c);
-        else store_pixel(F, static_cast<float4*>(out), i, c);
+        if (rgba8) store_pixel<P::kTrim>(F, static_cast<uint32_t*>(out), i, c);
+        else store_pixel<P::kTrim>(F, static_cast<float4*>(out), i, c);
     }
-    if (F.tile_cost && lane == 0) {  // this tile's duration: the next launch's dispatch order
-        const uint64_t dt = clock64() - t_start;
-        F.tile_cost[by * gridDim.x + bx] = dt > 0xffffffffull ? 0xffffffffu : (uint32_t)dt;
-    }
-    if constexpr (COUNT) {
-        if (F.evals_map && x < F.W && j < F.nrows) F.evals_map[(size_t)j * F.W + x] = cnt.evals;
-        uint32_t se = wave_sum_u32(cnt.evals), sf = wave_sum_u32(cnt.flop), ss = wave_sum_u32(cnt.skipped);
-        if (lane == 0) {
-            atomicAdd(&evals[0], (unsigned long long)se);
-            atomicAdd(&evals[1], (unsigned long long)sf);
-            if (ss) atomicAdd(&evals[2], (unsigned long long)ss);
-        }
-    }
+    if (F.tile_cost && lane == 0) F.tile_cost[by * gridDim.x + bx] = tile_clocks(t_start);
+    if constexpr (COUNT) store_tally(F, evals, cnt, x, j, lane);
 }
 }  // namespace rm
 extern "C" __global__ __launch_bounds__(64) void rm_plugin_render(rm::FrameConst F, void* out, int rgba8,

@@ -11,61 +11,23 @@
 
 namespace rm {
 
-// Scenes S0 and T use GLSL-precision hardware ops (v_rcp/v_sqrt/v_rsq and
-// pow = exp2(y*log2 x), as GPU GLSL compilers emit them); scene O keeps the
-// libm-accurate forms because its normal hash amplifies ulp differences.
-template <int SC>
-struct FastMath {
-    static constexpr bool value = SC == SCENE_T || SC == SCENE_S0;
-};
-template <int SC>
-__device__ __forceinline__ float mdiv(float a, float b) {
-    if constexpr (FastMath<SC>::value) return a * __builtin_amdgcn_rcpf(b);
-    else return a / b;
-}
-template <int SC>
-__device__ __forceinline__ float msqrt(float x) {
-    if constexpr (FastMath<SC>::value) return __builtin_amdgcn_sqrtf(x);
-    else return sqrtf(x);
-}
-template <int SC>
-__device__ __forceinline__ float mpow(float x, float y) {
-    if constexpr (FastMath<SC>::value) return __builtin_amdgcn_exp2f(y * __builtin_amdgcn_logf(x));
-    else return powf(x, y);
-}
-// Colour-only arithmetic (Phong's normalizations and pow, the shadow factor's
-// pow, the SSS term's pow, fog, tonemap, vignette): scenes O/OG and plugins
-// use the hardware exp2/log2/rsq/rcp forms there too (1-2 ulp).
-// Nothing that positions a ray or feeds the thickness hash changes (marches,
-// normals, the light direction and distance, the floor pattern keep their
-// exact forms), so ray-step counts are untouched and pixels move by ~1e-6.
-template <int SC>
-struct FastColour {
-    static constexpr bool value = true;  // (every scene: FastMath<SC> or the colour-only forms)
-};
-template <int SC>
-__device__ __forceinline__ float cpow(float x, float y) {
-    if constexpr (FastColour<SC>::value) return __builtin_amdgcn_exp2f(y * __builtin_amdgcn_logf(x));
-    else return powf(x, y);
-}
-template <int SC>
-__device__ __forceinline__ V3 cnormalize(V3 a) {
-    if constexpr (FastColour<SC>::value) return a * __builtin_amdgcn_rsqf(dot(a, a));
-    else return normalize(a);
-}
+// Colour-only normalization (Phong's vectors, the indirect light's direction:
+// v_rsq, every scene; ScenePolicy, rm_device.h)
+__device__ __forceinline__ V3 cnormalize(V3 a) { return a * __builtin_amdgcn_rsqf(dot(a, a)); }
 // the scene distance for marches and normals (exact for scene O), and for
 // the AO / shadow / thickness probes, whose results are smooth in the distance
 template <int SC, int NB = 3>
 __device__ __forceinline__ float dist_march(const FrameConst& F, V3 p, Tally& cnt) {
-    return scene_dist<SC, !FastMath<SC>::value, NB>(F, p, cnt);
+    return scene_dist<SC, ScenePolicy<SC>::kExactMarch, NB>(F, p, cnt);
 }
 template <int SC, int NB = 3>
 __device__ __forceinline__ float dist_probe(const FrameConst& F, V3 p, Tally& cnt) {
-    return scene_dist<SC, false, NB>(F, p, cnt);
+    return scene_dist<SC, kProbeForm, NB>(F, p, cnt);
 }
+// normals and light directions: v_rsq where the scene's marches use the hardware forms too
 template <int SC>
 __device__ __forceinline__ V3 mnormalize(V3 a) {
-    if constexpr (FastMath<SC>::value) return a * __builtin_amdgcn_rsqf(dot(a, a));
+    if constexpr (ScenePolicy<SC>::kHwMath) return a * __builtin_amdgcn_rsqf(dot(a, a));
     else return normalize(a);
 }
 
@@ -74,17 +36,15 @@ __device__ __forceinline__ V3 mnormalize(V3 a) {
 // slack / (1 + |d.y|) (1.01: directions up to 1 % off unit length); the probes
 // of a shading point (normal 0.0018, AO <= 0.8, thickness < 1 away) are all
 // plane-only when the slack there is >= 2.05.
-template <int SC>
-constexpr bool kPlaneSpans = SC == SCENE_O || SC == SCENE_OG;
 __device__ __forceinline__ float plane_rate(V3 d) {  // (v_rcp: 1 ulp is far inside the margin)
     return __builtin_amdgcn_rcpf(1.01f + fabsf(d.y));
 }
 template <int SC>
 __device__ __forceinline__ bool plane_probes(const FrameConst& F, V3 p) {
-    if constexpr (kPlaneSpans<SC>) {
+    if constexpr (ScenePolicy<SC>::kPlaneSpans) {
         Tally scratch;  // (not a ray-step of the reference)
         float slack;
-        (void)scene_dist_O<false>(p, sponge_space<false>(F, p), scratch, slack);
+        (void)scene_dist_O<kProbeForm>(p, sponge_space<kProbeForm>(F, p), scratch, slack);
         return slack >= 2.05f;
     } else {
         (void)F; (void)p;
@@ -94,7 +54,7 @@ __device__ __forceinline__ bool plane_probes(const FrameConst& F, V3 p) {
 // a probe's distance: EXACT = the march form (normals), else the probe form
 template <int SC, bool EXACT, int NB = 3>
 __device__ __forceinline__ float dist_at(const FrameConst& F, V3 p, Tally& cnt, bool plane) {
-    if constexpr (kPlaneSpans<SC>) {
+    if constexpr (ScenePolicy<SC>::kPlaneSpans) {
         if (plane) {
             cnt.evals++;
             return p.y;
@@ -108,10 +68,10 @@ __device__ __forceinline__ float dist_at(const FrameConst& F, V3 p, Tally& cnt, 
 template <int SC, int NB = 3>
 __device__ __forceinline__ V3 normal_fast(const FrameConst& F, V3 p, Tally& cnt, bool plane = false) {
     const float h = 0.001f;
-    float d0 = dist_at<SC, true, NB>(F, p + v3(h, -h, -h), cnt, plane);
-    float d1 = dist_at<SC, true, NB>(F, p + v3(-h, -h, h), cnt, plane);
-    float d2 = dist_at<SC, true, NB>(F, p + v3(-h, h, -h), cnt, plane);
-    float d3 = dist_at<SC, true, NB>(F, p + v3(h, h, h), cnt, plane);
+    float d0 = dist_at<SC, kExactForm, NB>(F, p + v3(h, -h, -h), cnt, plane);
+    float d1 = dist_at<SC, kExactForm, NB>(F, p + v3(-h, -h, h), cnt, plane);
+    float d2 = dist_at<SC, kExactForm, NB>(F, p + v3(-h, h, -h), cnt, plane);
+    float d3 = dist_at<SC, kExactForm, NB>(F, p + v3(h, h, h), cnt, plane);
     V3 g = v3(d0, -d0, -d0) + v3(-d1, -d1, d1);
     g = g + v3(-d2, d2, -d2);
     g = g + v3(d3, d3, d3);
@@ -127,7 +87,7 @@ __device__ __forceinline__ float cast_ray_d(const FrameConst& F, V3 ro, V3 rd, V
     float depth = ZNEAR;
     float res = 0.0f;
     bool hit = false;
-    if constexpr (kPlaneSpans<SC>) {
+    if constexpr (ScenePolicy<SC>::kPlaneSpans) {
         // depth < t_plane: sceneSDF is the floor plane, (ro + rd depth).y
         const float ia = plane_rate(rd);
         float t_plane = 0.0f, last = 0.0f;
@@ -140,7 +100,7 @@ __device__ __forceinline__ float cast_ray_d(const FrameConst& F, V3 ro, V3 rd, V
                 V3 q = ro + rd * depth;
                 float slack;
                 cnt.flop += FL_TRANSFORM;
-                res = scene_dist_O<true>(q, sponge_space<true>(F, q), cnt, slack);
+                res = scene_dist_O<kExactForm>(q, sponge_space<kExactForm>(F, q), cnt, slack);
                 t_plane = depth + slack * ia;
             }
             last = depth;
@@ -193,6 +153,10 @@ __device__ __forceinline__ float cast_ray_d(const FrameConst& F, V3 ro, V3 rd, V
 // changes res.  res^2 = 16 num / den (squared, as the loop keeps it).
 // oracle settle_test_O restates the rule and checks it on every step of the
 // reference's marches.
+constexpr float kSettleK = (2.9f / 1.01f) * (2.9f / 1.01f) / 16.0f;  // both settle rules, squared: res^2 = 16 num / den
+// (The slope of a Chebyshev term along the ray, d_i sign(q_i) on an axis
+// attaining max_i |q_i|, is spelled out twice here and once in
+// soft_shadow2_T_loop: as a shared function it compiled to other code.)
 __device__ __forceinline__ bool shadow_settled_O(const LinRay& w, const LinRay& s, float t, float maxt, float num,
                                                  float den) {
     const float L = maxt - t;
@@ -215,10 +179,9 @@ __device__ __forceinline__ bool shadow_settled_O(const LinRay& w, const LinRay& 
     const float a3 = p.y - 0.83f / 6.0f;  // plane
     const float g0 = fminf(fminf(a0, a1), fminf(a2, a3));
     const float g1 = fminf(fminf(fmaf(s0, L, a0), fmaf(s1, L, a1)), fminf(fmaf(s2, L, a2), fmaf(w.d.y, L, a3)));
-    constexpr float K = (2.9f / 1.01f) * (2.9f / 1.01f) / 16.0f;
     const float m = __builtin_elementwise_minimum(
-        __builtin_elementwise_minimum(__builtin_elementwise_minimum(g0, g1) - 0.1f, K * g0 * g0 * den - num * t * t),
-        K * g1 * g1 * den - num * maxt * maxt);
+        __builtin_elementwise_minimum(__builtin_elementwise_minimum(g0, g1) - 0.1f, kSettleK * g0 * g0 * den - num * t * t),
+        kSettleK * g1 * g1 * den - num * maxt * maxt);
     return m >= 0.0f;
 }
 
@@ -238,7 +201,7 @@ constexpr int kSettleOEvery = 8;  // steps between settle tests (a power of 2)
 template <int SC, int SM = 0, bool CAP = true>
 __device__ __forceinline__ float soft_shadow2_loop(const FrameConst& F, V3 ro, V3 rd, float mint, float maxt,
                                                    Tally& cnt) {
-    constexpr bool kSettle = kPlaneSpans<SC> && SM != 0;
+    constexpr bool kSettle = ScenePolicy<SC>::kSettleO && SM != 0;
     const LinRay w{ro, rd}, s = sponge_ray(F, ro, rd);
     float num = 1.0f / 16.0f, den = 1.0f, P = 0.0f, h = 1.0f;  // res = 1, k = 4
     float t = mint;
@@ -256,7 +219,7 @@ __device__ __forceinline__ float soft_shadow2_loop(const FrameConst& F, V3 ro, V
         } else {
             float slack;
             cnt.flop += FL_LINRAY;
-            h = scene_dist_O<false>(at(w, t), at(s, t), cnt, slack);
+            h = scene_dist_O<kProbeForm>(at(w, t), at(s, t), cnt, slack);
             t_plane = t + slack * ia;
         }
         float h2 = h * h;
@@ -329,6 +292,10 @@ __device__ __forceinline__ float soft_shadow2(const FrameConst& F, V3 ro, V3 rd,
 // measures 43-55 % of scene T's shadow steps after it.  The instrumented
 // kernels (COUNT) keep every step: their ray-step counts and maps are the
 // reference's.
+// (The candidate update is soft_shadow2_loop's and the slope on the axis
+// attaining the Chebyshev max is shadow_settled_O's, restated: as shared
+// functions they compiled to other code, here or in a scene plugin.  Change
+// them together.)
 // SM: 0 no settle test, 1 leave the march when settled (timed kernels), 2 run
 // the test and count the steps after it in cnt.skipped (instrumented kernels:
 // every reference step is still taken and counted)
@@ -351,7 +318,7 @@ __device__ __forceinline__ float soft_shadow2_T_loop(const FrameConst& F, const 
         cnt.evals++;
         cnt.flop += FL_LINRAY + FL_BOX;
         if constexpr (SM == 2) cnt.skipped += was_settled ? 1u : 0u;
-        h = sponge_folds<false, NB>(q, box, cnt.flop);
+        h = sponge_folds<ScenePolicy<SCENE_T>::kExactMarch, NB>(q, box, cnt.flop);
         float h2 = h * h;
         float Q = it == 1 ? 1.0f : fmaf(P, P, -h2);
         float D = it == 1 ? t : fmaf(t, P, -h2);
@@ -368,9 +335,8 @@ __device__ __forceinline__ float soft_shadow2_T_loop(const FrameConst& F, const 
                 const float sz = q.z < 0.0f ? -s.d.z : s.d.z;
                 const float sl = ax == m ? sx : ay == m ? sy : sz;
                 const float be = fmaf(sl, maxt - t, box);
-                constexpr float K = (2.9f / 1.01f) * (2.9f / 1.01f) / 16.0f;  // res^2 = 16 num / den
-                settled = (box >= 0.1f) & (h + h >= P) & (sl >= 0.0f) & (K * box * box * den >= num * t * t) &
-                          (K * be * be * den >= num * maxt * maxt);
+                settled = (box >= 0.1f) & (h + h >= P) & (sl >= 0.0f) & (kSettleK * box * box * den >= num * t * t) &
+                          (kSettleK * be * be * den >= num * maxt * maxt);
             }
         }
         if constexpr (SM == 1) {
@@ -430,9 +396,8 @@ __device__ __forceinline__ float cast_ray_T(const FrameConst& F, const LinRay& s
 // Scenes O/OG form the probe points of AO and thickness, and
 // the sphere / cube lengths of the probe-form distance, with fused
 // multiply-adds (these results are smooth in their roundings; the exact march
-// and normal paths, and the thickness hash of the normal, keep the GLSL's)
-template <int SC>
-constexpr bool kProbeFma = kPlaneSpans<SC>;
+// and normal paths, and the thickness hash of the normal, keep the GLSL's):
+// ScenePolicy<SC>::kProbeFma
 __device__ __forceinline__ V3 fma3(V3 a, float s, V3 b) {  // a s + b, one rounding per component
     return v3(fmaf(a.x, s, b.x), fmaf(a.y, s, b.y), fmaf(a.z, s, b.z));
 }
@@ -455,10 +420,10 @@ __device__ __forceinline__ float ao_real(const FrameConst& F, V3 pos, V3 n, Tall
         return sum / maxSum;
     }
     auto probe = [&](int i) {
-        V3 p = kProbeFma<SC> ? fma3(n, (float)(i + 1) * 0.2f, pos) : pos + (n * (float)(i + 1)) * 0.2f;
-        sum += (1.0f / (float)(1 << i)) * dist_at<SC, false, NB>(F, p, cnt, plane);
+        V3 p = ScenePolicy<SC>::kProbeFma ? fma3(n, (float)(i + 1) * 0.2f, pos) : pos + (n * (float)(i + 1)) * 0.2f;
+        sum += (1.0f / (float)(1 << i)) * dist_at<SC, kProbeForm, NB>(F, p, cnt, plane);
     };
-    if constexpr (kPlaneSpans<SC>) {
+    if constexpr (ScenePolicy<SC>::kPlaneSpans) {
 #pragma unroll 1
         for (int i = 0; i < 4; i++) probe(i);
     } else {
@@ -474,15 +439,14 @@ __device__ __forceinline__ float ao_real(const FrameConst& F, V3 pos, V3 n, Tall
 
 // common.frag:730-754 (N = the caller's normal; L = normalize(lightPos - p),
 // the caller's light direction, the same value)
-template <int SC>
 __device__ __forceinline__ V3 phong(V3 k_d, V3 k_s, float alpha, V3 L, V3 p, V3 eye, V3 N) {
-    V3 V = cnormalize<SC>(eye - p);
-    V3 R = cnormalize<SC>(reflect(-L, N));
+    V3 V = cnormalize(eye - p);
+    V3 R = cnormalize(reflect(-L, N));
     float dotLN = dot(L, N);
     float dotRV = dot(R, V);
     if (dotLN < 0.0f) return v3s(0.0f);
     if (dotRV < 0.0f) return k_d * dotLN;
-    return k_d * dotLN + k_s * cpow<SC>(dotRV, alpha);
+    return k_d * dotLN + k_s * gpow(dotRV, alpha);
 }
 
 // Soft shadows of points facing away from the light: phong returns 0 when
@@ -510,19 +474,16 @@ __device__ __forceinline__ float shadow_if_lit(float dotLN, Tally& cnt, March ma
     }
 }
 
-template <int SC>
+// pow(vec3(sha), vec3(1.0, 1.2, 1.5)): pow(x, 1) = x; one log2 shared by the other two
 __device__ __forceinline__ V3 shadow_pow(float sha) {
-    if constexpr (FastColour<SC>::value) {  // pow(x, 1) = x; one log2 shared by the other two
-        const float l = __builtin_amdgcn_logf(sha);
-        return v3(sha, __builtin_amdgcn_exp2f(1.2f * l), __builtin_amdgcn_exp2f(1.5f * l));
-    }
-    return v3(mpow<SC>(sha, 1.0f), mpow<SC>(sha, 1.2f), mpow<SC>(sha, 1.5f));
+    const float l = __builtin_amdgcn_logf(sha);
+    return v3(sha, __builtin_amdgcn_exp2f(1.2f * l), __builtin_amdgcn_exp2f(1.5f * l));
 }
 
 // output_shader.frag:85-116
 template <int SC>
 __device__ __forceinline__ float thickness(const FrameConst& F, V3 pos, V3 norm, Tally& cnt, bool plane) {
-    if constexpr (kPlaneSpans<SC>) {
+    if constexpr (ScenePolicy<SC>::kPlaneSpans) {
         // A floor point whose probes are all plane-only: every sample is
         // pos.y + (sampleDir * sampleLength).y, and the sample directions depend
         // on the normal alone, which the floor's tetrahedral gradient makes
@@ -545,15 +506,15 @@ __device__ __forceinline__ float thickness(const FrameConst& F, V3 pos, V3 norm,
         // so it is normalized with v_rsq (~1 ulp) instead of a correctly
         // rounded sqrt and division: -22 VALU per sample, 32 samples
         const V3 hd = hash33(nn + v3s(fi)) - v3s(0.5f);
-        if constexpr (kProbeFma<SC>) {
+        if constexpr (ScenePolicy<SC>::kProbeFma) {
             const V3 rnd = hd * __builtin_amdgcn_rsqf(dot_fma(hd, hd));
             const V3 dir = fma3(nn * -2.0f, fminf(0.0f, dot_fma(rnd, nn)), rnd);  // reflectVector (:70-73)
-            th += sl + dist_at<SC, false>(F, fma3(dir, sl, pos), cnt, plane);
+            th += sl + dist_at<SC, kProbeForm>(F, fma3(dir, sl, pos), cnt, plane);
             continue;
         }
         V3 rnd = hd * __builtin_amdgcn_rsqf(dot(hd, hd));
         V3 dir = rnd - (nn * 2.0f) * fminf(0.0f, dot(rnd, nn));  // reflectVector (:70-73)
-        th += sl + dist_at<SC, false>(F, pos + dir * sl, cnt, plane);
+        th += sl + dist_at<SC, kProbeForm>(F, pos + dir * sl, cnt, plane);
     }
     return clamp01(th * 0.03125f);
 }
@@ -574,16 +535,15 @@ __device__ __forceinline__ V3 light_O(const FrameConst& F, V3 mq, V3 ro, V3 rd, 
     float th = thickness<SC>(F, p, n, cnt, plane);
     mat = scene_mat<SC>(F, mq);
     float sky = clamp01(0.5f + 0.5f * n.y);
-    float ind = clamp01(dot(n, cnormalize<SC>(lightDir * v3(-1.0f, 0.0f, -1.0f))));
-    V3 shading =
-        phong<SC>(v3(1.64f, 1.27f, 0.99f), mat.specular, mat.shininess, lightDir, p, ro, phongN) * shadow_pow<SC>(sha);
+    float ind = clamp01(dot(n, cnormalize(lightDir * v3(-1.0f, 0.0f, -1.0f))));
+    V3 shading = phong(v3(1.64f, 1.27f, 0.99f), mat.specular, mat.shininess, lightDir, p, ro, phongN) * shadow_pow(sha);
     shading = shading + v3(0.16f, 0.20f, 0.28f) * sky * occ;
     shading = shading + v3(0.40f, 0.28f, 0.20f) * ind * occ;
     V3 sssl = lightDir + n * 0.6f;
-    float sssdot = cpow<SC>(clamp01(dot(-rd, -sssl)), 1.1f) * 0.3f;
+    float sssdot = gpow(clamp01(dot(-rd, -sssl)), 1.1f) * 0.3f;
     shading = shading + v3s((sssdot + 0.3f) * th);
     V3 color = mat.diffuse * shading + mat.emission;
-    return apply_scattering<FastColour<SC>::value>(color, ro, p);
+    return apply_scattering<ScenePolicy<SC>::kTrim>(color, ro, p);
 }
 
 // output_shader.frag:218-230
@@ -607,7 +567,7 @@ __device__ __forceinline__ V3 render_reflection(const FrameConst& F, V3 ro, V3 r
         V3 n = normal_fast<SC>(F, p, cnt, pl);
         return light_O<SC, SETTLE>(F, q, ro, rd, p, n, n, pl, m, cnt);
     }
-    return background(ro, rd);
+    return background<ScenePolicy<SC>::kTrim>(ro, rd);
 }
 
 // output_shader.frag:298-343 (MAX_REFRACTIONS 4); live only in test scene OG
@@ -621,7 +581,7 @@ __device__ __forceinline__ V3 render_refraction(const FrameConst& F, V3 ro, V3 r
         float dist = invert < 0.0f ? cast_ray_d<SC, true>(F, ro, rd, q, cnt) : cast_ray_d<SC, false>(F, ro, rd, q, cnt);
         if (invert < 0.0f) absorb += dist;
         if (dist < 0.0f) {
-            if (invert > 0.0f) color = color + background(ro, rd);
+            if (invert > 0.0f) color = color + background<ScenePolicy<SC>::kTrim>(ro, rd);
             break;
         }
         Mat m;
@@ -639,13 +599,10 @@ __device__ __forceinline__ V3 render_refraction(const FrameConst& F, V3 ro, V3 r
         ro = p + rd * (0.01f / fabsf(dot(rd, n)));
         invert = tif ? invert : -invert;
     }
-    if constexpr (FastColour<SC>::value) {
-        constexpr float kLog2e = 1.4426950408889634f;
-        return color * v3(__builtin_amdgcn_exp2f(-absorption.x * absorb * kLog2e),
-                          __builtin_amdgcn_exp2f(-absorption.y * absorb * kLog2e),
-                          __builtin_amdgcn_exp2f(-absorption.z * absorb * kLog2e));
-    }
-    return color * v3(expf(-absorption.x * absorb), expf(-absorption.y * absorb), expf(-absorption.z * absorb));
+    constexpr float kLog2e = 1.4426950408889634f;  // exp(-absorption * absorb), colour only (ScenePolicy)
+    return color * v3(__builtin_amdgcn_exp2f(-absorption.x * absorb * kLog2e),
+                      __builtin_amdgcn_exp2f(-absorption.y * absorb * kLog2e),
+                      __builtin_amdgcn_exp2f(-absorption.z * absorb * kLog2e));
 }
 
 // output_shader.frag:348-385 (SETTLE: soft_shadow2's SM)
@@ -653,7 +610,7 @@ template <int SC, int SETTLE = 0>
 __device__ __forceinline__ V3 render_O(const FrameConst& F, V3 ro, V3 rd, Tally& cnt) {
     V3 q;
     float dist = cast_ray_d<SC, false>(F, ro, rd, q, cnt);
-    if (!(dist > 0.0f)) return background(ro, rd);
+    if (!(dist > 0.0f)) return background<ScenePolicy<SC>::kTrim>(ro, rd);
     Mat m;
     V3 p = ro + rd * dist;
     const bool pl = plane_probes<SC>(F, p);
@@ -679,12 +636,13 @@ __device__ __forceinline__ V3 render_O(const FrameConst& F, V3 ro, V3 rd, Tally&
 template <int NB = 3, int SETTLE = 0, int RSTOP = 0>
 __device__ __forceinline__ V3 render_T(const FrameConst& F, V3 ro, V3 rd, Tally& cnt) {
     constexpr int SC = SCENE_T;
+    using P = ScenePolicy<SC>;
     // ro is the camera, u_pos: its sponge-space image is the frame's, F.camq_* (rm_device.h camera_sponge_origin)
     float qx = F.camq_x, qy = F.camq_y, qz = F.camq_z;
     // (in VGPRs, as the lanes' own results were: an SGPR addend makes the march's three FMAs per step the slow
     // issue form)
     asm volatile("" : "+v"(qx), "+v"(qy), "+v"(qz));
-    const LinRay prim{v3(qx, qy, qz), sponge_rot<false>(F, rd.x, rd.y, rd.z)};
+    const LinRay prim{v3(qx, qy, qz), sponge_rot<P::kExactMarch>(F, rd.x, rd.y, rd.z)};
     V3 p = ro + rd * cast_ray_T<NB>(F, prim, cnt);
     V3 n = normal_fast<SC, NB>(F, p, cnt);
     // getColorReflect (common.frag:991-1002); its dead nr normal is skipped
@@ -694,7 +652,7 @@ __device__ __forceinline__ V3 render_T(const FrameConst& F, V3 ro, V3 rd, Tally&
     // |pr - p| >= 0.01 (the offset of ror; the march adds depth >= ZNEAR along rdir): far above 2^-96, below
     // which alone sqrtf's rescaling acts, so the bare v_sqrt_f32 is length()'s float (apply_scattering, TRIM)
     const V3 pd = pr - p;
-    float c = clamp01_as<true>(__builtin_amdgcn_sqrtf(dot(pd, pd)) * (1.0f / 3.0f));
+    float c = clamp01_as<P::kTrim>(__builtin_amdgcn_sqrtf(dot(pd, pd)) * (1.0f / 3.0f));
     const V3 lightPos = v3(20.0f, 50.0f, 0.0f);
     V3 Ld = lightPos - p;
     float ld2 = dot(Ld, Ld);
@@ -714,13 +672,13 @@ __device__ __forceinline__ V3 render_T(const FrameConst& F, V3 ro, V3 rd, Tally&
     if (__builtin_amdgcn_ballot_w64(sha != 1.0f) != 0) {
         float s = sha;
         asm volatile("" : "+v"(s));
-        spow = shadow_pow<SC>(s);
+        spow = shadow_pow(s);
     }
-    V3 shading = phong<SC>(v3(1.64f, 1.27f, 0.99f), v3(1.0f, 1.0f, 0.0f), 1280.0f, lightDir, p, ro, n) * spow;
+    V3 shading = phong(v3(1.64f, 1.27f, 0.99f), v3(1.0f, 1.0f, 0.0f), 1280.0f, lightDir, p, ro, n) * spow;
     shading = shading + v3(0.16f, 0.20f, 0.28f) * sky * occ;
     shading = shading + v3(0.40f, 0.28f, 0.20f) * ind * occ;
     shading = shading + v3s(fre * occ);
-    return apply_scattering<true, true>(v3s(c) * shading, ro, p);
+    return apply_scattering<P::kTrim>(v3s(c) * shading, ro, p);
 }
 
 // BASELINE config-1 scene S0: castRayD + normal + lambert
@@ -734,7 +692,7 @@ __device__ __forceinline__ V3 render_S0(const FrameConst& F, V3 ro, V3 rd, Tally
         V3 lightDir = mnormalize<SC>(v3(20.0f, 50.0f, 0.0f) - p);
         return v3(0.2f, 0.02f, 0.02f) * (0.1f + clamp01(dot(n, lightDir)));
     }
-    return background<true>(ro, rd);  // (|rd ZFAR|^2 ~ 2500: apply_scattering's TRIM)
+    return background<ScenePolicy<SC>::kTrim>(ro, rd);  // (|rd ZFAR|^2 ~ 2500: apply_scattering's TRIM)
 }
 
 // Camera (output_shader.frag:388-404): gl_TexCoord at the pixel centre.
@@ -782,7 +740,7 @@ __device__ __forceinline__ void camera_ray(const FrameConst& F, int x, int y, fl
 // (the first frame of a still camera) stores the colour: the target needs no
 // clearing.
 // SAT (scenes S0/T): the RGBA8 word from the saturating packed converts (rm_device.h pack_rgb8_opaque).
-template <bool SAT = false, typename OUT>
+template <bool SAT, typename OUT>
 __device__ __forceinline__ void store_pixel(const FrameConst& F, OUT* __restrict__ out, size_t i, V3 c) {
 #pragma clang fp contract(off)
     if (F.accumulate && F.sample_part < 1.0f) {
@@ -814,6 +772,29 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
     return v;
 }
 
+// The frame around a tile's pixels, shared by render_tile_at below and the
+// scene plugins' plugin_render_tile (rm_plugin_kernels.h).  (Their
+// dispatch-order lookup, tile_order -> (bx, by), is stated in both: as a
+// shared function it compiled to other code, a commuted multiply.  Change
+// them together.)
+// a one-wave tile's duration in shader clocks, for F.tile_cost: the next launch's dispatch order
+__device__ __forceinline__ uint32_t tile_clocks(uint64_t t_start) {
+    const uint64_t dt = clock64() - t_start;
+    return dt > 0xffffffffull ? 0xffffffffu : (uint32_t)dt;
+}
+// instrumented launches: pixel (x, packed row j)'s ray-steps into the step map,
+// the wave's tallies into evals[0..2]
+__device__ __forceinline__ void store_tally(const FrameConst& F, unsigned long long* evals, const Tally& cnt, int x,
+                                            int j, int lane) {
+    if (F.evals_map && x < F.W && j < F.nrows) F.evals_map[(size_t)j * F.W + x] = cnt.evals;
+    uint32_t se = wave_sum_u32(cnt.evals), sf = wave_sum_u32(cnt.flop), ss = wave_sum_u32(cnt.skipped);
+    if (lane == 0) {
+        atomicAdd(&evals[0], (unsigned long long)se);
+        atomicAdd(&evals[1], (unsigned long long)sf);
+        if (ss) atomicAdd(&evals[2], (unsigned long long)ss);
+    }
+}
+
 // SETTLE: the timed kernels' exact early exits (1), which the instrumented
 // (COUNT) kernels do not take but count (2): their ray-step counts and maps
 // stay the reference's, rm_stats.skipped the steps the timed kernels leave out
@@ -834,7 +815,7 @@ __device__ __forceinline__ void scene_eval_one(const FrameConst& F, const float*
     if (i >= n) return;
     const V3 p = v3(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]);
     Tally t;
-    dist[i] = scene_dist<SC, true>(F, p, t);
+    dist[i] = scene_dist<SC, kExactForm>(F, p, t);
     if (mat) {
         const Mat m = scene_mat<SC>(F, p);
         const float v[16] = {m.diffuse.x,    m.diffuse.y,    m.diffuse.z,    m.specular.x,    m.specular.y,  m.specular.z,
@@ -868,6 +849,7 @@ template <int SC, bool COUNT, int K, typename OUT>
 __device__ __forceinline__ void render_tile_at(const FrameConst& F, OUT* __restrict__ out,
                                                unsigned long long* __restrict__ evals, int bx, int by, int gx) {
     using T = Tiling<K>;
+    using P = ScenePolicy<SC>;
     const uint64_t t_start = T::WPB == 1 && F.tile_cost ? clock64() : 0;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     // scene T: the first lat_tiles workgroups of an ordered launch are its
@@ -893,8 +875,8 @@ __device__ __forceinline__ void render_tile_at(const FrameConst& F, OUT* __restr
         const int y = shard_row(F, F.row0 + j);
         float tcx, tcy;
         V3 ro, rd;
-        camera_ray<FastMath<SC>::value>(F, x, y, tcx, tcy, ro, rd);
-        const float vig = vignette<FastColour<SC>::value>(tcx, tcy);
+        camera_ray<P::kHwMath>(F, x, y, tcx, tcy, ro, rd);
+        const float vig = vignette(tcx, tcy);
         V3 c;
         if constexpr (SC == SCENE_T) {
             // (no settle exit in the latency tiles: their long grazing shadow marches
@@ -904,29 +886,17 @@ __device__ __forceinline__ void render_tile_at(const FrameConst& F, OUT* __restr
             else c = render_pixel<SC, 3, COUNT ? 2 : 1, COUNT ? 2 : 1>(F, ro, rd, cnt);
         } else {
             (void)lat;
-            c = render_pixel<SC, 3, kPlaneSpans<SC> ? (COUNT ? 2 : 1) : 0>(F, ro, rd, cnt);
+            c = render_pixel<SC, 3, P::kSettleO ? (COUNT ? 2 : 1) : 0>(F, ro, rd, cnt);
         }
-        constexpr bool kTrim = FastMath<SC>::value;  // scenes S0/T: one-instruction clamps, saturating pack
-        c = post_colour<FastColour<SC>::value, kTrim>(c, vig);
-        if constexpr (kWire) wire_px = kTrim ? pack_rgb8_opaque(c.x, c.y, c.z) : pack_rgba8(c.x, c.y, c.z, 1.0f);
-        else store_pixel<kTrim>(F, out, (size_t)j * F.W + x, c);
+        c = post_colour<P::kTrim>(c, vig);
+        if constexpr (kWire) wire_px = P::kTrim ? pack_rgb8_opaque(c.x, c.y, c.z) : pack_rgba8(c.x, c.y, c.z, 1.0f);
+        else store_pixel<P::kTrim>(F, out, (size_t)j * F.W + x, c);
     }
     if constexpr (kWire)
         wire_encode_tile(wire_px, reinterpret_cast<WireTile*>(out), (long long)gx * ((F.nrows + 7) / 8),
                          (long long)by * gx + bx);
-    if (T::WPB == 1 && F.tile_cost && lane == 0) {  // this tile's duration: the next launch's dispatch order
-        const uint64_t dt = clock64() - t_start;
-        F.tile_cost[by * gx + bx] = dt > 0xffffffffull ? 0xffffffffu : (uint32_t)dt;
-    }
-    if constexpr (COUNT) {
-        if (F.evals_map && x < F.W && j < F.nrows) F.evals_map[(size_t)j * F.W + x] = cnt.evals;
-        uint32_t se = wave_sum_u32(cnt.evals), sf = wave_sum_u32(cnt.flop), ss = wave_sum_u32(cnt.skipped);
-        if (lane == 0) {
-            atomicAdd(&evals[0], (unsigned long long)se);
-            atomicAdd(&evals[1], (unsigned long long)sf);
-            if (ss) atomicAdd(&evals[2], (unsigned long long)ss);
-        }
-    }
+    if (T::WPB == 1 && F.tile_cost && lane == 0) F.tile_cost[by * gx + bx] = tile_clocks(t_start);
+    if constexpr (COUNT) store_tally(F, evals, cnt, x, j, lane);
 }
 
 template <int SC, bool COUNT, int K, typename OUT>
