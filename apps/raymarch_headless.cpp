@@ -6,13 +6,18 @@
 // Input comes from a script instead of SFML events: one character per frame,
 // W/A/S/D/U(p)/N(down) move as the reference's WASD/Space/LShift
 // (main.cpp:111-126,155-171), '.' = no key; --mouse dx,dy adds a per-frame
-// mouse delta (main.cpp:86-97).  The FXAA/bloom passes and the ImGui overlay
-// stay out of scope (they remain on the reference's GL path).
+// mouse delta (main.cpp:86-97).  --post runs the reference's post passes after
+// each frame (main.cpp:209-214: post.frag into postTexture, bloom of it back
+// into outputTexture) through rm::PostShader / rm::PostBloom; --post-sample and
+// --tonemap stand for an edit of post.frag's main().  The ImGui overlay stays
+// out of scope.  With --post, --ppm writes the frame after the post passes.
 //
 // Usage: raymarch_headless [--scene output_shader.frag] [--w 1600] [--h 900]
 //          [--frames 60] [--script WWWWDD..] [--mouse 3,0] [--time-freeze]
 //          [--steps 128] [--ppm out.ppm] [--gpus N] [--band 16] [--accumulate]
 //          [--format rgba8|float] [--stats] [--warmup N]
+//          [--post] [--post-sample fxaa|chromatic|texel]
+//          [--tonemap none|aces|reinhard|jodie|uncharted2]
 // Frames are drawn into the RGBA8 target the reference renders into
 // (--format float: RGBA32F) and queued without a host synchronization per
 // frame; --stats times each frame's kernel (HIP events, which waits for every
@@ -23,6 +28,7 @@
 // takes that path with one GPU too.
 #include <chrono>
 #include <cmath>
+#include <initializer_list>
 #include <memory>
 #include <cstdio>
 #include <cstdlib>
@@ -39,6 +45,18 @@ int main(int argc, char** argv) {
     int mdx = 0, mdy = 0;
     bool time_freeze = false, sharded = false, accumulate = false, stats = false, fmt_float = false;
     int warmup = 0;
+    bool post = false;
+    rm_post_sample post_sample = RM_POST_SAMPLE_FXAA;
+    rm_tonemap tonemap = RM_TONEMAP_NONE;
+    // a name of `names` -> its index, or -1
+    auto choice = [](const std::string& v, std::initializer_list<const char*> names) {
+        int k = 0;
+        for (const char* n : names) {
+            if (v == n) return k;
+            k++;
+        }
+        return -1;
+    };
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() { return i + 1 < argc ? std::string(argv[++i]) : std::string(); };
@@ -64,6 +82,23 @@ int main(int argc, char** argv) {
             }
             fmt_float = f == "float";
         }
+        else if (a == "--post") post = true;
+        else if (a == "--post-sample") {
+            const int k = choice(next(), {"fxaa", "texel", "chromatic"});  // rm_post_sample's order
+            if (k < 0) {
+                std::fprintf(stderr, "--post-sample fxaa|chromatic|texel\n");
+                return 2;
+            }
+            post_sample = (rm_post_sample)k;
+        }
+        else if (a == "--tonemap") {
+            const int k = choice(next(), {"none", "aces", "reinhard", "jodie", "uncharted2"});  // rm_tonemap's order
+            if (k < 0) {
+                std::fprintf(stderr, "--tonemap none|aces|reinhard|jodie|uncharted2\n");
+                return 2;
+            }
+            tonemap = (rm_tonemap)k;
+        }
         else if (a == "--mouse") std::sscanf(next().c_str(), "%d,%d", &mdx, &mdy);
         else {
             std::fprintf(stderr, "unknown argument %s\n", a.c_str());
@@ -83,6 +118,10 @@ int main(int argc, char** argv) {
     }
     if (accumulate && (gpus > 1 || sharded)) {
         std::fprintf(stderr, "--accumulate renders on one GPU\n");
+        return 2;
+    }
+    if (post && (gpus > 1 || sharded || accumulate || fmt_float)) {
+        std::fprintf(stderr, "--post runs on the one-GPU RGBA8 target, without --accumulate\n");
         return 2;
     }
     // one shader (librm context) per GPU; the first is the reference's `shader`
@@ -112,6 +151,22 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "cannot allocate the %dx%d target on %d GPU(s): %s\n", w, h, gpus,
                      shader.lastError().c_str());
         return 1;
+    }
+
+    // main.cpp:48-50,56-61
+    rm::RenderTexture postTexture;
+    rm::PostShader post_shader(shader);
+    rm::PostBloom post_bloom(shader);
+    if (post) {
+        if (!postTexture.create(w, h)) {
+            std::fprintf(stderr, "cannot allocate the %dx%d post target\n", w, h);
+            return 1;
+        }
+        if (!rm::ShaderLoader::loadFromFile("post.frag", rm::Shader::Fragment, post_shader)) return 1;
+        post_shader.setUniform("u_resolution", rm::Vec2{wf, hf});
+        post_shader.setSample(post_sample);
+        post_shader.setTonemap(tonemap);
+        post_bloom.init(rm::Vec2{wf, hf});
     }
 
     std::mt19937 e2(20261015);
@@ -163,6 +218,13 @@ int main(int argc, char** argv) {
         if (!drawn) {
             std::fprintf(stderr, "draw failed: %s\n", shader.lastError().c_str());
             return 1;
+        }
+        if (post) {  // main.cpp:209-214
+            post_shader.setUniform("u_main_tex", outputTexture);
+            if (!postTexture.draw(post_shader) || !post_bloom.apply(postTexture, outputTexture)) {
+                std::fprintf(stderr, "post passes failed: %s\n", post_shader.lastError().c_str());
+                return 1;
+            }
         }
         float slowest = 0.0f;
         for (const rm_stats& x : st) slowest = x.kernel_ms > slowest ? x.kernel_ms : slowest;

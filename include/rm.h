@@ -299,6 +299,39 @@ rm_status rm_bloom(rm_ctx *ctx, int W, int H, const uint32_t *in, uint32_t *out)
  * asynchronous on the context's stream; bloom's scratch as rm_bloom's. */
 rm_status rm_post_chain(rm_ctx *ctx, int W, int H, const uint32_t *in, uint32_t *mid, uint32_t *out);
 
+/* post.frag's main() (:135-144) with the choices a user of the reference makes
+ * by editing its one statement (the menu of post.frag:63-131):
+ *   uv    = (tc.x, 1 - tc.y)                    the output is the input flipped vertically
+ *   color = fxaa(tex, uv, res)                                         RM_POST_SAMPLE_FXAA
+ *         | texture(tex, uv)                                           RM_POST_SAMPLE_TEXEL
+ *         | vec4(chromaticAberration(tex, uv), texture(tex, uv).a)     RM_POST_SAMPLE_CHROMATIC
+ *   color.rgb = tonemap_X(color.rgb)            X: rm_tonemap (NONE: no statement)
+ *   gl_FragColor = color                        one RGBA8 store
+ * Sampler and contract as rm_fxaa: nearest, clamp to edge, u_resolution = (W,
+ * H); in/out W*H RGBA8 words (device, distinct), W*H < 2^30; asynchronous on
+ * the context's stream.  (FXAA, NONE) is rm_fxaa, byte for byte.  A sample or
+ * tonemap value outside its enum -> RM_ERR_INVALID_ARGUMENT. */
+typedef enum rm_post_sample {
+    RM_POST_SAMPLE_FXAA = 0,
+    RM_POST_SAMPLE_TEXEL = 1,
+    RM_POST_SAMPLE_CHROMATIC = 2
+} rm_post_sample;
+
+typedef enum rm_tonemap {
+    RM_TONEMAP_NONE = 0,
+    RM_TONEMAP_ACES = 1,           /* tonemapACES, post.frag:67-75 */
+    RM_TONEMAP_REINHARD = 2,       /* tonemapReinhard, :77-80 */
+    RM_TONEMAP_REINHARD_JODIE = 3, /* tonemapReinhardJodie, :82-88 */
+    RM_TONEMAP_UNCHARTED2 = 4      /* tonemapUncharted2Filmic, :90-109 */
+} rm_tonemap;
+
+rm_status rm_post_frag(rm_ctx *ctx, int W, int H, int sample, int tonemap, const uint32_t *in, uint32_t *out);
+
+/* rm_post_chain with that pass in FXAA's place: rm_post_frag(in -> mid), then
+ * rm_bloom(mid -> out), in one call; (FXAA, NONE) gives rm_post_chain's bytes. */
+rm_status rm_post_chain_ex(rm_ctx *ctx, int W, int H, int sample, int tonemap, const uint32_t *in, uint32_t *mid,
+                           uint32_t *out);
+
 /* The render kernels' code objects by content (16 hex digits of a SHA-256 of
  * the translation units that hold them): rocprofv3 counters of a render launch
  * (profiles/pmc_counters.json) name the build they counted, and bench.py

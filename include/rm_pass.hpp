@@ -11,6 +11,21 @@
 //   t.draw(sprite, &shader);                           t.draw(shader);
 //   t.getTexture()                                     t.textureRGBA8() (device RGBA8) / t.copyToHostRGBA8(...)
 //
+// and the post passes of main.cpp:56-61,209-214:
+//
+//   sf::Shader post_shader;                            rm::PostShader post_shader(shader);
+//   ShaderLoader::loadFromFile("post.frag", ..., post_shader)   the same call (the name is checked)
+//   post_shader.setUniform("u_resolution", Vector2f)   post_shader.setUniform("u_resolution", rm::Vec2{...})
+//   post_shader.setUniform("u_main_tex", t.getTexture())   post_shader.setUniform("u_main_tex", t)
+//   (an edit of post.frag's main)                      post_shader.setSample(...), setTonemap(...)
+//   postTexture.draw(sprite, &post_shader);            postTexture.draw(post_shader);
+//   PostBloom post_bloom; post_bloom.init(Vector2f)    rm::PostBloom post_bloom(shader); post_bloom.init(rm::Vec2{...})
+//   postTexture.setSmooth(true); generateMipmap();     (part of apply)
+//   post_bloom.apply(postTexture.getTexture(), out, sprite)   post_bloom.apply(postTexture, out)
+//
+// The post objects run on the context (and stream) of the rm::Shader they are
+// made from, so a frame's passes are ordered as the reference's GL calls are.
+//
 // Errors follow the reference: loadFromFile prints and returns false
 // (source/shader_loader.cpp:26-30); other calls return false and keep the
 // message in lastError().  Header-only; link with librm.so.
@@ -20,6 +35,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -75,6 +91,53 @@ private:
     int device_ = 0;
 };
 
+class RenderTexture;
+
+// post.frag as main.cpp:56-58,209-210 drives it: the pass is rm_post_frag on the
+// context of the ray-march shader.  The reference's user chooses the sample
+// and the tonemap operator by editing post.frag's main(); here they are
+// setSample / setTonemap (the defaults are post.frag as shipped: FXAA, none).
+class PostShader {
+public:
+    explicit PostShader(Shader& pass) : pass_(pass) {}
+    bool valid() const { return pass_.valid(); }
+    rm_ctx* ctx() { return pass_.ctx(); }
+    std::string lastError() const { return error_.empty() ? pass_.lastError() : error_; }
+
+    bool setUniform(const char* name, Vec2 v) {
+        if (std::strcmp(name, "u_resolution") != 0) return unknown(name);
+        resolution_ = v;
+        return true;
+    }
+    bool setUniform(const char* name, RenderTexture& texture) {
+        if (std::strcmp(name, "u_main_tex") != 0) return unknown(name);
+        main_tex_ = &texture;
+        return true;
+    }
+    void setSample(rm_post_sample s) { sample_ = s; }
+    void setTonemap(rm_tonemap t) { tonemap_ = t; }
+    rm_post_sample sample() const { return sample_; }
+    rm_tonemap tonemap() const { return tonemap_; }
+    Vec2 resolution() const { return resolution_; }
+    RenderTexture* mainTexture() { return main_tex_; }
+    void markLoaded() { loaded_ = true; }
+    bool loaded() const { return loaded_; }
+    bool fail(const std::string& msg) {
+        error_ = msg;
+        return false;
+    }
+
+private:
+    bool unknown(const char* name) { return fail(std::string("rm::PostShader: post.frag has no uniform ") + name); }
+    Shader& pass_;
+    Vec2 resolution_{0.0f, 0.0f};
+    RenderTexture* main_tex_ = nullptr;
+    rm_post_sample sample_ = RM_POST_SAMPLE_FXAA;
+    rm_tonemap tonemap_ = RM_TONEMAP_NONE;
+    bool loaded_ = false;
+    std::string error_;
+};
+
 struct ShaderLoader {
     // source/shader_loader.h:11
     static bool loadFromFile(const char* file_name, Shader::Type, Shader& out_shader) {
@@ -83,6 +146,18 @@ struct ShaderLoader {
             return false;
         }
         return rm_load_scene(out_shader.ctx(), file_name) == RM_OK;  // prints its own message on failure
+    }
+    // main.cpp:57: the post shader is post.frag (any directory); no file is read,
+    // the pass is compiled into librm.so
+    static bool loadFromFile(const char* file_name, Shader::Type, PostShader& out_shader) {
+        const char* base = std::strrchr(file_name, '/');
+        base = base ? base + 1 : file_name;
+        if (!out_shader.valid() || std::strcmp(base, "post.frag") != 0) {
+            std::fprintf(stderr, "ShaderLoader: can't load file %s (the post shader is post.frag)\n", file_name);
+            return false;
+        }
+        out_shader.markLoaded();
+        return true;
     }
 };
 
@@ -118,10 +193,25 @@ public:
                               : rm_render_accumulate(shader.ctx(), w_, h_, static_cast<float*>(tex_), stats)) ==
                RM_OK;
     }
+    // RenderTarget::draw(sprite, &post_shader) (main.cpp:210): post.frag over the
+    // shader's u_main_tex into this RGBA8 target (rm_post_frag)
+    bool draw(PostShader& post) {
+        RenderTexture* src = post.mainTexture();
+        if (!post.loaded())
+            return post.fail("rm::PostShader: not loaded (ShaderLoader::loadFromFile(\"post.frag\", ...))");
+        if (!src || !src->textureRGBA8() || !textureRGBA8())
+            return post.fail("rm::PostShader: u_main_tex and the target must be RGBA8 textures");
+        if (src->w_ != w_ || src->h_ != h_ || post.resolution().x != (float)w_ || post.resolution().y != (float)h_)
+            return post.fail("rm::PostShader: u_resolution, u_main_tex and the target must have one size");
+        post.fail("");  // (clear: a failure below is the library's message)
+        return rm_post_frag(post.ctx(), w_, h_, post.sample(), post.tonemap(), src->textureRGBA8(), textureRGBA8()) ==
+               RM_OK;
+    }
     Format format() const { return fmt_; }
     // the device target: RGBA8 words (R in the low byte) or RGBA32F texels;
     // asking for the other format's view returns null and says so once
     uint32_t* textureRGBA8() { return fmt_ == RGBA8 ? static_cast<uint32_t*>(tex_) : mismatch<uint32_t>("RGBA8"); }
+    const uint32_t* textureRGBA8() const { return fmt_ == RGBA8 ? static_cast<const uint32_t*>(tex_) : nullptr; }
     float* texture() { return fmt_ == RGBA32F ? static_cast<float*>(tex_) : mismatch<float>("RGBA32F"); }
     int width() const { return w_; }
     int height() const { return h_; }
@@ -164,6 +254,25 @@ private:
     int w_ = 0, h_ = 0;
     Format fmt_ = RGBA8;
     bool warned_ = false;
+};
+
+// source/post_bloom.h: bloom.frag over a texture's mip chain (rm_bloom), on the
+// context of the ray-march shader
+class PostBloom {
+public:
+    explicit PostBloom(Shader& pass) : pass_(pass) {}
+    void init(Vec2 resolution) { resolution_ = resolution; }
+    // main.cpp:212-214: setSmooth + generateMipmap of `src` are part of the pass
+    bool apply(const RenderTexture& src, RenderTexture& dst) {
+        if (!src.textureRGBA8() || !dst.textureRGBA8() || src.width() != dst.width() || src.height() != dst.height() ||
+            resolution_.x != (float)src.width() || resolution_.y != (float)src.height())
+            return false;
+        return rm_bloom(pass_.ctx(), src.width(), src.height(), src.textureRGBA8(), dst.textureRGBA8()) == RM_OK;
+    }
+
+private:
+    Shader& pass_;
+    Vec2 resolution_{0.0f, 0.0f};
 };
 
 // The multi-GPU form of RenderTexture::draw: a W x H RGBA8 frame whose row

@@ -7,7 +7,7 @@ this package is the host-side mirror of the reference's
 ShaderLoader / sf::Shader / RenderTexture surface plus the row-sharded
 multi-GPU frame (``frame.py``).
 """
-from ._lib import EXPORTS, LIB_PATH, RmError, lib  # noqa: F401
+from ._lib import EXPORTS, LIB_PATH, POST_SAMPLES, TONEMAPS, RmError, lib  # noqa: F401
 from .api import (Comm, Renderer, RenderTexture, Shader, ShaderLoader, comm_get_id, compile_scene,  # noqa: F401
                   cycle_rows, shard_rows, sharded_layout, wire_capacity, render_code_hash, wire_workspace_bytes)
 from .poses import POSES, S0_POSE  # noqa: F401

@@ -23,7 +23,8 @@ EXPORTS = ("rm_create", "rm_destroy", "rm_load_scene", "rm_set_uniform1f", "rm_s
            "rm_synchronize",
            "rm_render", "rm_render_band", "rm_render_rows", "rm_shard_rows", "rm_deinterleave", "rm_deinterleave_rgba8",
            "rm_pack_rgba8", "rm_pack_rgb8", "rm_deinterleave_rgb8",
-           "rm_render_rgba8", "rm_render_accumulate", "rm_render_accumulate_rgba8", "rm_render_band_rgba8", "rm_render_rows_rgba8", "rm_fxaa", "rm_bloom", "rm_post_chain", "rm_render_code_hash", "rm_render_cycle_rows_wire", "rm_last_error", "rm_status_string",
+           "rm_render_rgba8", "rm_render_accumulate", "rm_render_accumulate_rgba8", "rm_render_band_rgba8", "rm_render_rows_rgba8", "rm_fxaa", "rm_bloom", "rm_post_chain", "rm_post_frag", "rm_post_chain_ex",
+           "rm_render_code_hash", "rm_render_cycle_rows_wire", "rm_last_error", "rm_status_string",
            "rm_compile_scene", "rm_scene_eval", "rm_render_step_map", "rm_sharded_layout", "rm_comm_get_id",
            "rm_comm_init_rank", "rm_comm_init_all", "rm_comm_destroy", "rm_render_sharded", "rm_render_sharded_all",
            "rm_set_tile_order", "rm_tile_grid", "rm_comm_info", "rm_abi_version", "rm_cycle_rows",
@@ -34,6 +35,9 @@ EXPORTS = ("rm_create", "rm_destroy", "rm_load_scene", "rm_set_uniform1f", "rm_s
 # include/rm.h RM_ABI_VERSION: the struct layouts below
 ABI_VERSION = 3
 DISPATCH = {0: "row-major", 1: "explicit", 2: "adaptive"}
+# include/rm.h rm_post_sample, rm_tonemap (rm_post_frag, rm_post_chain_ex)
+POST_SAMPLES = {"fxaa": 0, "texel": 1, "chromatic": 2}
+TONEMAPS = {"none": 0, "aces": 1, "reinhard": 2, "jodie": 3, "uncharted2": 4}
 
 
 class RmParams(ctypes.Structure):
@@ -122,6 +126,8 @@ def lib() -> ctypes.CDLL:
         "rm_fxaa": ([vp, c.c_int, c.c_int, vp, vp], c.c_int),
         "rm_bloom": ([vp, c.c_int, c.c_int, vp, vp], c.c_int),
         "rm_post_chain": ([vp, c.c_int, c.c_int, vp, vp, vp], c.c_int),
+        "rm_post_frag": ([vp, c.c_int, c.c_int, c.c_int, c.c_int, vp, vp], c.c_int),
+        "rm_post_chain_ex": ([vp, c.c_int, c.c_int, c.c_int, c.c_int, vp, vp, vp], c.c_int),
         "rm_render_code_hash": ([], cp),
         "rm_render_cycle_rows_wire": ([vp, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, vp, vp, vp,
                                        c.POINTER(RmStats)], c.c_int),

@@ -377,9 +377,37 @@ class Renderer:
         check(lib().rm_bloom(self._ctx, W, H, self._ptr(frame8), self._ptr(out)), self._ctx)
         return out
 
-    def post_chain(self, frame8, mid=None, out=None):
+    @staticmethod
+    def _post_choice(sample, tonemap):
+        """(sample, tonemap) names or rm.h values -> values; an int passes
+        through for the library to judge."""
+        def value(v, table, what):
+            if isinstance(v, str):
+                if v not in table:
+                    raise ValueError(f"{what} must be one of {sorted(table)}, not {v!r}")
+                return table[v]
+            return int(v)
+        return value(sample, _lib.POST_SAMPLES, "sample"), value(tonemap, _lib.TONEMAPS, "tonemap")
+
+    def post_frag(self, frame8, sample="fxaa", tonemap="none", out=None):
+        """post.frag's main() over an [H, W] RGBA8 (int32 words) device frame
+        with its sample ("fxaa", "texel", "chromatic": POST_SAMPLES) and tonemap
+        operator (TONEMAPS) chosen (rm_post_frag); the defaults are fxaa()."""
+        torch = _torch()
+        s, t = self._post_choice(sample, tonemap)
+        H, W = frame8.shape
+        if out is None:
+            out = torch.empty_like(frame8)
+        _check_out(frame8, H * W)
+        _check_out(out, H * W)
+        check(lib().rm_post_frag(self._ctx, W, H, s, t, self._ptr(frame8), self._ptr(out)), self._ctx)
+        return out
+
+    def post_chain(self, frame8, mid=None, out=None, sample="fxaa", tonemap="none"):
         """main.cpp:209-214's post passes of a frame: FXAA of frame8 into mid,
-        then bloom of mid into out (rm_post_chain); returns (mid, out)."""
+        then bloom of mid into out (rm_post_chain); returns (mid, out).  With a
+        sample or tonemap other than the defaults the first pass is post_frag's
+        (rm_post_chain_ex)."""
         torch = _torch()
         H, W = frame8.shape
         if mid is None:
@@ -388,7 +416,12 @@ class Renderer:
             out = torch.empty_like(frame8)
         for t in (frame8, mid, out):
             _check_out(t, H * W)
-        check(lib().rm_post_chain(self._ctx, W, H, self._ptr(frame8), self._ptr(mid), self._ptr(out)), self._ctx)
+        if (sample, tonemap) == ("fxaa", "none"):
+            check(lib().rm_post_chain(self._ctx, W, H, self._ptr(frame8), self._ptr(mid), self._ptr(out)), self._ctx)
+        else:
+            s, t = self._post_choice(sample, tonemap)
+            check(lib().rm_post_chain_ex(self._ctx, W, H, s, t, self._ptr(frame8), self._ptr(mid), self._ptr(out)),
+                  self._ctx)
         return mid, out
 
     def scene_eval(self, points, material: bool = False):

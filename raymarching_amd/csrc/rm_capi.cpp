@@ -5,6 +5,8 @@
 #include <cstdio>
 #include <cstring>
 #include <fstream>
+#include <initializer_list>
+#include <string>
 
 #include "rm_ctx.h"
 #include "rm_internal.h"
@@ -575,6 +577,60 @@ rm_status rm_post_chain(rm_ctx *ctx, int W, int H, const uint32_t *in, uint32_t 
     // (the mips from FXAA's registers measured slower)
     hipError_t e = rm::launch_fxaa(in, mid, W, H, ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "post chain: fxaa launch");
+    e = rm::launch_bloom(mid, out, ctx->mips, plan, ctx->stream, cached);
+    if (e != hipSuccess) return hip_fail(ctx, e, "post chain: bloom launch");
+    bloom_done(ctx, W, H);
+    mark_done(ctx);
+    return RM_OK;
+}
+
+static_assert(RM_POST_SAMPLE_FXAA == rm::kSampleFxaa && RM_POST_SAMPLE_TEXEL == rm::kSampleTexel &&
+                  RM_POST_SAMPLE_CHROMATIC == rm::kSampleChromatic && RM_POST_SAMPLE_CHROMATIC + 1 == rm::kSampleCount,
+              "rm_post_sample and the kernels' kSample*");
+static_assert(RM_TONEMAP_NONE == rm::kTonemapNone && RM_TONEMAP_ACES == rm::kTonemapAces &&
+                  RM_TONEMAP_REINHARD == rm::kTonemapReinhard && RM_TONEMAP_REINHARD_JODIE == rm::kTonemapJodie &&
+                  RM_TONEMAP_UNCHARTED2 == rm::kTonemapUncharted2 && RM_TONEMAP_UNCHARTED2 + 1 == rm::kTonemapCount,
+              "rm_tonemap and the kernels' kTonemap*");
+
+// what rm_post_frag and rm_post_chain_ex check alike (`who` names the call)
+static rm_status post_frag_args(rm_ctx *ctx, const char *who, int W, int H, int sample, int tonemap, bool distinct,
+                                std::initializer_list<const uint32_t *> bufs) {
+    auto bad = [&](const char *what) { return fail(ctx, RM_ERR_INVALID_ARGUMENT, std::string(who) + ": " + what); };
+    for (const uint32_t *p : bufs)
+        if (!p) return bad("bad arguments");
+    if (W <= 0 || H <= 0 || !distinct) return bad("bad arguments");
+    if (sample < 0 || sample >= rm::kSampleCount) return bad("unknown sample (rm_post_sample)");
+    if (tonemap < 0 || tonemap >= rm::kTonemapCount) return bad("unknown tonemap (rm_tonemap)");
+    if ((int64_t)W * H >= ((int64_t)1 << 30))  // the kernels' 32-bit byte offsets
+        return bad("frame of 2^30 texels or more");
+    for (const uint32_t *p : bufs)
+        if (!is_device_ptr(p)) return bad("device pointers required");
+    return RM_OK;
+}
+
+rm_status rm_post_frag(rm_ctx *ctx, int W, int H, int sample, int tonemap, const uint32_t *in, uint32_t *out) {
+    if (!ctx) return RM_ERR_INVALID_ARGUMENT;
+    if (rm_status st = post_frag_args(ctx, "rm_post_frag", W, H, sample, tonemap, in != out, {in, out})) return st;
+    return launch_on(ctx, "post_frag launch", [&] {
+        rm::TraceRange range("rm_post_frag");
+        return rm::launch_post_frag(in, out, W, H, sample, tonemap, ctx->stream);
+    });
+}
+
+rm_status rm_post_chain_ex(rm_ctx *ctx, int W, int H, int sample, int tonemap, const uint32_t *in, uint32_t *mid,
+                           uint32_t *out) {
+    if (!ctx) return RM_ERR_INVALID_ARGUMENT;
+    if (rm_status st = post_frag_args(ctx, "rm_post_chain_ex", W, H, sample, tonemap,
+                                      in != mid && mid != out && in != out, {in, mid, out}))
+        return st;
+    RM_HIP(hipSetDevice(ctx->device));
+    rm::TraceRange range("rm_post_chain_ex");
+    const rm::BloomPlan plan = rm::bloom_plan(W, H);
+    bool cached = false;
+    if (rm_status st = bloom_scratch(ctx, plan, W, H, cached)) return st;
+    // main.cpp:209-214 with the edited post.frag: the pass into postTexture, bloom of it
+    hipError_t e = rm::launch_post_frag(in, mid, W, H, sample, tonemap, ctx->stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "post chain: post_frag launch");
     e = rm::launch_bloom(mid, out, ctx->mips, plan, ctx->stream, cached);
     if (e != hipSuccess) return hip_fail(ctx, e, "post chain: bloom launch");
     bloom_done(ctx, W, H);

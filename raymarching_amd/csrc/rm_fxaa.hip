@@ -26,9 +26,14 @@
 // FXAA kernel (0.0721-0.0729 -> 0.0697-0.0706 ms) but slows bloom's
 // (profiles/r05/post_ilp_ab.log).
 #include "rm_post_common.h"
+#include "rm_post_tonemap.h"
 
 namespace rm {
 
+// TM: the tonemap operator applied to the float colour before the store
+// (rm_post_frag with sample FXAA); kTonemapNone is post.frag as
+// shipped (rm_fxaa)
+template <int TM>
 __device__ __forceinline__ uint32_t fxaa_px(const uint32_t* __restrict__ in, int W, int H, int x, int y) {
     const float FXAA_REDUCE_MIN = 1.0f / 128.0f, FXAA_REDUCE_MUL = 1.0f / 8.0f, FXAA_SPAN_MAX = 8.0f;
     // post.frag:138: uv = vec2(gl_TexCoord.x, 1 - gl_TexCoord.y)
@@ -59,7 +64,7 @@ __device__ __forceinline__ uint32_t fxaa_px(const uint32_t* __restrict__ in, int
     RGB b = RGB{a.r * 0.5f + (s3.r + s4.r) * 0.25f, a.g * 0.5f + (s3.g + s4.g) * 0.25f,
                 a.b * 0.5f + (s3.b + s4.b) * 0.25f};
     float lB = luma(b);
-    RGB c = (lB < lMin || lB > lMax) ? a : b;
+    RGB c = tonemap<TM>((lB < lMin || lB > lMax) ? a : b);
     float alpha = (float)(tM >> 24) * (1.0f / 255.0f);
     return unorm8(c.r) | (unorm8(c.g) << 8) | (unorm8(c.b) << 16) | (unorm8(alpha) << 24);
 }
@@ -68,6 +73,7 @@ __device__ __forceinline__ uint32_t fxaa_px(const uint32_t* __restrict__ in, int
 // tile): the kernel is latency-bound (two dependent rounds of L2 taps per
 // pixel), so each lane keeps four pixels' taps in flight at once.
 constexpr int FXAA_TX = 64, FXAA_TY = 16, FXAA_PX = 4;
+template <int TM>
 __global__ __launch_bounds__(256) void rm_fxaa_kernel(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
                                                        int W, int H) {
     const int x = blockIdx.x * FXAA_TX + (threadIdx.x & 63);
@@ -77,7 +83,7 @@ __global__ __launch_bounds__(256) void rm_fxaa_kernel(const uint32_t* __restrict
 #pragma unroll
     for (int k = 0; k < FXAA_PX; k++) {
         const int y = y0 + 4 * k;
-        r[k] = fxaa_px(in, W, H, x, y < H ? y : H - 1);  // straight-line: the four pixels' taps overlap
+        r[k] = fxaa_px<TM>(in, W, H, x, y < H ? y : H - 1);  // straight-line: the four pixels' taps overlap
     }
 #pragma unroll
     for (int k = 0; k < FXAA_PX; k++) {
@@ -124,6 +130,7 @@ __device__ __forceinline__ int floor_i32(float v) {  // (int)floorf(v) for |v| <
     asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(r) : "v"(v));
     return r;
 }
+template <int TM>
 __global__ __launch_bounds__(FXL_NT) void rm_fxaa_lds_kernel(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
                                                           int W, int H) {
     __shared__ uint32_t stex[FXL_H * FXL_W];
@@ -233,7 +240,11 @@ __global__ __launch_bounds__(FXL_NT) void rm_fxaa_lds_kernel(const uint32_t* __r
         // exactly, luma(b) = lM lies in [lMin, lMax], c = s, and unorm8 of
         // byte / 255 is the byte again for all 256 bytes: the output is tM.
         // Taken when the wave's whole block is short-span.
-        if (__builtin_amdgcn_ballot_w64(fmaxf(fabsf(dxs), fabsf(dys)) > 0.5f) == 0) return tM;
+        // (with a tonemap operator the pixel is tonemap(texel))
+        if (__builtin_amdgcn_ballot_w64(fmaxf(fabsf(dxs), fabsf(dys)) > 0.5f) == 0) {
+            if constexpr (TM == kTonemapNone) return tM;
+            else return pack_rgb_alpha_of(tonemap<TM>(rgb(tM)), tM);
+        }
         dx = dxs * ivx;
         dy = dys * ivy;
         RGB s1 = span_tap(fx + dx * k1, fy + dy * k1);
@@ -244,10 +255,10 @@ __global__ __launch_bounds__(FXL_NT) void rm_fxaa_lds_kernel(const uint32_t* __r
         RGB b = RGB{a.r * 0.5f + (s3.r + s4.r) * 0.25f, a.g * 0.5f + (s3.g + s4.g) * 0.25f,
                     a.b * 0.5f + (s3.b + s4.b) * 0.25f};
         float lB = luma(b);
-        RGB c = (lB < lMin || lB > lMax) ? a : b;
+        RGB c = tonemap<TM>((lB < lMin || lB > lMax) ? a : b);
         // (the colour is finite: unorm8 inputs, a correctly rounded, positive rcpDirMin;
         // alpha stays the texel's own byte: (b / 255) * 255 rounds back to b)
-        return unorm8_finite(c.r) | (unorm8_finite(c.g) << 8) | (unorm8_finite(c.b) << 16) | (tM & 0xff000000u);
+        return pack_rgb_alpha_of(c, tM);
     };
     // two blocks at a time: their dependent chains (LDS taps -> division -> span
     // taps) interleave
@@ -260,16 +271,25 @@ __global__ __launch_bounds__(FXL_NT) void rm_fxaa_lds_kernel(const uint32_t* __r
     }
 }
 
-hipError_t launch_fxaa(const uint32_t* in, uint32_t* out, int W, int H, hipStream_t s) {
+template <int TM>
+static hipError_t launch_fxaa_tm(const uint32_t* in, uint32_t* out, int W, int H, hipStream_t s) {
     if (W <= 0 || H <= 0) return hipSuccess;
     if (W <= FXL_MAX_DIM && H <= FXL_MAX_DIM) {
         dim3 grid((W + FXL_TX - 1) / FXL_TX, (H + FXL_TY - 1) / FXL_TY);
-        hipLaunchKernelGGL(rm_fxaa_lds_kernel, grid, dim3(FXL_NT), 0, s, in, out, W, H);
+        hipLaunchKernelGGL(rm_fxaa_lds_kernel<TM>, grid, dim3(FXL_NT), 0, s, in, out, W, H);
         return hipGetLastError();
     }
     dim3 grid((W + FXAA_TX - 1) / FXAA_TX, (H + FXAA_TY - 1) / FXAA_TY);
-    hipLaunchKernelGGL(rm_fxaa_kernel, grid, dim3(256), 0, s, in, out, W, H);
+    hipLaunchKernelGGL(rm_fxaa_kernel<TM>, grid, dim3(256), 0, s, in, out, W, H);
     return hipGetLastError();
+}
+
+hipError_t launch_fxaa(const uint32_t* in, uint32_t* out, int W, int H, hipStream_t s) {
+    return launch_fxaa_tm<kTonemapNone>(in, out, W, H, s);
+}
+
+hipError_t launch_fxaa_tonemap(const uint32_t* in, uint32_t* out, int W, int H, int tonemap, hipStream_t s) {
+    return with_tonemap(tonemap, [&](auto tm) { return launch_fxaa_tm<decltype(tm)::value>(in, out, W, H, s); });
 }
 
 }  // namespace rm

@@ -54,6 +54,15 @@ hipError_t launch_deinterleave_cycle_rgb8(const uint8_t* gathered, uint32_t* out
 hipError_t launch_tile_order(const uint32_t* cost, int n, int gx, int radius, uint32_t* order, uint32_t* hist,
                              uint32_t* next, uint8_t* bucket, hipStream_t s);
 hipError_t launch_fxaa(const uint32_t* in, uint32_t* out, int W, int H, hipStream_t s);
+// post.frag's main() with a choice of sample and tonemap operator (rm_post_frag,
+// DESIGN.md 2.18); the values are rm.h's rm_post_sample / rm_tonemap
+constexpr int kSampleFxaa = 0, kSampleTexel = 1, kSampleChromatic = 2, kSampleCount = 3;
+constexpr int kTonemapNone = 0, kTonemapAces = 1, kTonemapReinhard = 2, kTonemapJodie = 3, kTonemapUncharted2 = 4,
+              kTonemapCount = 5;
+// rm_fxaa.hip: FXAA with the operator applied to its float colour before the store
+hipError_t launch_fxaa_tonemap(const uint32_t* in, uint32_t* out, int W, int H, int tonemap, hipStream_t s);
+// rm_post_frag.hip: the texel and chromaticAberration samples
+hipError_t launch_post_frag(const uint32_t* in, uint32_t* out, int W, int H, int sample, int tonemap, hipStream_t s);
 // rm_wire.hip: the compressed RGB wire of RGBA8 row parts
 long long wire_capacity(int W, int n);
 long long wire_workspace(int W, int n);

@@ -1,7 +1,7 @@
 // rm_post_common.h -- what the post passes (rm_fxaa.hip: FXAA, post.frag;
-// rm_post.hip: bloom, bloom.frag) share: the texel fetch and unpacking of an
+// rm_post_frag.hip: post.frag's other samples; rm_post.hip: bloom, bloom.frag) share: the texel fetch and unpacking of an
 // RGBA8 frame in GL's unorm8 semantics, luma, and the RGBA8 store's rounding.
-// Both translation units are built without FMA contraction and with
+// These translation units are built without FMA contraction and with
 // correctly rounded division, so their float paths are bit-identical to
 // oracle/rm_oracle.c.
 #pragma once
