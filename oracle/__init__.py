@@ -70,7 +70,7 @@ def lib(fast: bool = False) -> ctypes.CDLL:
         L.oracle_render_pixels.argtypes = [ctypes.c_int, up, ctypes.c_int, ctypes.c_int, i32p, ctypes.c_int, f32p,
                                            u32p]
         L.oracle_render_pixels.restype = ctypes.c_int
-        for fn in ("oracle_scene_dist", "oracle_normal"):
+        for fn in ("oracle_scene_dist", "oracle_scene_mat", "oracle_normal"):
             getattr(L, fn).argtypes = [ctypes.c_int, up, f32p, ctypes.c_int, f32p]
             getattr(L, fn).restype = ctypes.c_int
         for fn, n in (("oracle_glsl_mod", 2), ("oracle_glsl_smoothstep", 3), ("oracle_sdbox", 6),
@@ -228,6 +228,18 @@ def scene_dist(scene: str, pts, **kw):
     u = uniforms(1, 1, **kw)
     lib().oracle_scene_dist(SCENES[scene], ctypes.byref(u), _p(pts, ctypes.c_float), len(pts),
                             _p(out, ctypes.c_float))
+    return out
+
+
+def scene_mat(scene: str, pts, **kw):
+    """sceneSDF's Material at points [n, 3] -> [n, 16] float32 (diffuse, specular,
+    shininess, reflectivity, transparency, absorption, refraction_index,
+    emission: rm_scene_eval's order)."""
+    pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 3)
+    out = np.zeros((len(pts), 16), np.float32)
+    u = uniforms(1, 1, **kw)
+    lib().oracle_scene_mat(SCENES[scene], ctypes.byref(u), _p(pts, ctypes.c_float), len(pts),
+                           _p(out, ctypes.c_float))
     return out
 
 

@@ -1020,6 +1020,23 @@ int oracle_scene_dist(int scene, const oracle_uniforms *u, const float *pts, int
     return 0;
 }
 
+/* sceneSDF's Material at explicit points (n x 3 in, n x 16 out): the fields of
+ * struct Material (common.frag:20-35) in declaration order — KAT entry. */
+int oracle_scene_mat(int scene, const oracle_uniforms *u, const float *pts, int n, float *out) {
+    Ctx C;
+    uint64_t cnt = 0;
+    init_ctx(&C, scene, u);
+    C.evals = &cnt;
+    for (int i = 0; i < n; i++) {
+        const Material m = sceneSDF(&C, v3(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2])).mat;
+        const float v[16] = {m.diffuse.x, m.diffuse.y, m.diffuse.z, m.specular.x, m.specular.y, m.specular.z,
+                             m.shininess, m.reflectivity, m.transparency, m.absorption.x, m.absorption.y,
+                             m.absorption.z, m.refraction_index, m.emission.x, m.emission.y, m.emission.z};
+        memcpy(out + 16 * (size_t)i, v, sizeof(v));
+    }
+    return 0;
+}
+
 /* Normal at explicit points — KAT entry. */
 int oracle_normal(int scene, const oracle_uniforms *u, const float *pts, int n, float *out) {
     Ctx C;

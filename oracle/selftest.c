@@ -22,6 +22,7 @@ int oracle_render(int scene, const oracle_uniforms *u, int W, int H, int row0, i
 int oracle_render_diag(int scene, const oracle_uniforms *u, int W, int H, int row0, int nrows, float *diag, float *out);
 int oracle_fxaa(int W, int H, const uint32_t *in, uint32_t *out, float *out_f32);
 int oracle_bloom(int W, int H, const uint32_t *in, uint32_t *out, uint32_t *mips);
+int oracle_scene_mat(int scene, const oracle_uniforms *u, const float *pts, int n, float *out);
 
 int main(void) {
     const int sizes[][2] = {{1, 1}, {7, 3}, {33, 17}, {64, 40}};
@@ -48,6 +49,11 @@ int main(void) {
                     px[i] = (c == c ? (uint32_t)(fminf(fmaxf(c, 0.0f), 1.0f) * 255.0f) : 0u) * 0x010101u | 0xff000000u;
                 }
                 if (oracle_fxaa(W, H, px, o, NULL) || oracle_bloom(W, H, px, o, NULL)) return 1;
+                /* sceneSDF's Material at W*H points (the frame's floats as coordinates), 16 floats each */
+                float *pts = malloc(sizeof(float) * 3 * W * H), *mat = malloc(sizeof(float) * 16 * W * H);
+                for (int i = 0; i < 3 * W * H; i++) pts[i] = 8.0f * img[i] - 2.0f;
+                if (oracle_scene_mat(scene, &u, pts, W * H, mat)) return 1;
+                free(pts), free(mat);
                 checked += W * H;
                 free(img), free(ev), free(px), free(o);
             }

@@ -220,7 +220,10 @@ def test_builtin_scene_eval_matches_oracle(R, scene):
     R.set_uniform("u_time", 1.25)
     d = R.scene_eval(pts)
     o = oracle.scene_dist(scene, pts, time=1.25)
-    assert np.mean(_within(d, o, 1e-5, 1e-5)) >= 0.999, np.abs(d - o).max()
+    if scene == "O":  # its translation unit rounds like the GLSL: the same float (tests/test_scene_o_skips.py)
+        assert np.array_equal(d, o), (int((d != o).sum()), np.abs(d - o).max())
+    else:
+        assert np.mean(_within(d, o, 1e-5, 1e-5)) >= 0.999, np.abs(d - o).max()
 
 
 @pytest.mark.gpu
