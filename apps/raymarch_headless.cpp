@@ -18,6 +18,11 @@
 //          [--format rgba8|float] [--stats] [--warmup N]
 //          [--post] [--post-sample fxaa|chromatic|texel]
 //          [--tonemap none|aces|reinhard|jodie|uncharted2]
+//          [--uniform name=v[,v...]]...
+// --uniform sets a uniform the scene declares itself (a scene plugin's
+// `uniform vec4 u_ball = ...;`, rm.h rm_load_scene) once the scene is loaded:
+// one to four numbers for a float / vec2 / vec3 / vec4, one for an int or a
+// bool; repeatable.
 // Frames are drawn into the RGBA8 target the reference renders into
 // (--format float: RGBA32F) and queued without a host synchronization per
 // frame; --stats times each frame's kernel (HIP events, which waits for every
@@ -48,6 +53,11 @@ int main(int argc, char** argv) {
     bool post = false;
     rm_post_sample post_sample = RM_POST_SAMPLE_FXAA;
     rm_tonemap tonemap = RM_TONEMAP_NONE;
+    struct UniformArg {
+        std::string name;
+        std::vector<double> v;
+    };
+    std::vector<UniformArg> uniform_args;
     // a name of `names` -> its index, or -1
     auto choice = [](const std::string& v, std::initializer_list<const char*> names) {
         int k = 0;
@@ -100,6 +110,26 @@ int main(int argc, char** argv) {
             tonemap = (rm_tonemap)k;
         }
         else if (a == "--mouse") std::sscanf(next().c_str(), "%d,%d", &mdx, &mdy);
+        else if (a == "--uniform") {
+            const std::string u = next();
+            const size_t eq = u.find('=');
+            UniformArg arg;
+            arg.name = u.substr(0, eq);
+            const char* p = eq == std::string::npos ? "" : u.c_str() + eq + 1;
+            while (*p) {
+                char* end = nullptr;
+                const double x = std::strtod(p, &end);
+                if (end == p || (*end != ',' && *end != '\0')) break;
+                arg.v.push_back(x);
+                p = *end ? end + 1 : end;
+                if (!*end) break;
+            }
+            if (arg.name.empty() || *p || arg.v.empty() || arg.v.size() > 4) {
+                std::fprintf(stderr, "--uniform name=v[,v[,v[,v]]]\n");
+                return 2;
+            }
+            uniform_args.push_back(arg);
+        }
         else {
             std::fprintf(stderr, "unknown argument %s\n", a.c_str());
             return 2;
@@ -137,6 +167,25 @@ int main(int argc, char** argv) {
         if (!rm::ShaderLoader::loadFromFile(scene.c_str(), rm::Shader::Fragment, s)) return 1;
         s.setUniform("u_resolution", rm::Vec2{wf, hf});
         s.setMarchSteps(steps);
+        for (const UniformArg& u : uniform_args) {
+            // the declared type decides between the float and the int call
+            rm_uniform_info info;
+            int n = 0, type = RM_UNIFORM_FLOAT;
+            rm_uniform_count(s.ctx(), &n);
+            for (int k = 0; k < n; k++)
+                if (rm_uniform_info_at(s.ctx(), k, &info) == RM_OK && u.name == info.name) type = info.type;
+            const float x = (float)u.v[0], y = u.v.size() > 1 ? (float)u.v[1] : 0.0f,
+                        z = u.v.size() > 2 ? (float)u.v[2] : 0.0f, q = u.v.size() > 3 ? (float)u.v[3] : 0.0f;
+            const bool set = type != RM_UNIFORM_FLOAT && u.v.size() == 1 ? s.setUniform(u.name.c_str(), (int)u.v[0])
+                             : u.v.size() == 1 ? s.setUniform(u.name.c_str(), x)
+                             : u.v.size() == 2 ? s.setUniform(u.name.c_str(), rm::Vec2{x, y})
+                             : u.v.size() == 3 ? s.setUniform(u.name.c_str(), rm::Vec3{x, y, z})
+                                               : s.setUniform(u.name.c_str(), rm::Vec4{x, y, z, q});
+            if (!set) {
+                std::fprintf(stderr, "--uniform %s: %s\n", u.name.c_str(), s.lastError().c_str());
+                return 1;
+            }
+        }
         all.push_back(&s);
     }
     rm::Shader& shader = *all[0];

@@ -130,7 +130,28 @@ rm_status rm_destroy(rm_ctx *ctx);
  * hiprtc into output_shader.frag's pass around that scene (the reference's
  * "Reload scene shader", main.cpp:134-139).  A compile error prints the log
  * and returns RM_ERR_SCENE, keeping the previous scene.  Unknown name and no
- * file -> RM_ERR_FILE; another existing file -> RM_ERR_SCENE. */
+ * file -> RM_ERR_FILE; another existing file -> RM_ERR_SCENE.
+ *
+ * A scene plugin (a .hip file or an edited scene part) may declare uniforms
+ * of its own beside the pass's, at file scope (outside braces, parentheses,
+ * comments, string literals and preprocessor lines):
+ *     uniform <type> <name>;           type: float vec2 vec3 vec4 int bool
+ *     uniform <type> <name> = <init>;  a signed literal, true/false, or
+ *                                      vecN(literals) with 1 or N arguments
+ *     uniform <ftype> <name>[N];       ftype: float vec2 vec3 vec4; N = 1..64
+ * Without an initialiser, and for arrays, the value starts at zero.  The scene
+ * reads a uniform as an rvalue of its type and an array element as name[i]
+ * with any int i; writing to one does not compile.  Anything else (an
+ * expression initialiser, several names in one declaration, sampler2D, an
+ * int or bool array, N outside 1..64, a name of the pass such as u_time, a
+ * name longer than 63 characters, more than 64 slots of 16 bytes -- one per
+ * uniform, one per array element) is RM_ERR_SCENE with a file:line: message.
+ * The declarations are matched in the text, before the compiler's
+ * preprocessor runs: one inside an inactive #if region still creates the
+ * uniform.  A successful load sets every uniform to its declaration's
+ * default, also when the same file is loaded again; a failed load keeps the
+ * previous scene, its uniforms and their values.  A built-in scene declares
+ * none. */
 rm_status rm_load_scene(rm_ctx *ctx, const char *file_name);
 
 /* Compile a scene file as rm_load_scene would, without loading it (no GPU
@@ -153,10 +174,43 @@ rm_status rm_scene_eval(rm_ctx *ctx, const float *points, int64_t n, float *dist
  * declared but unused by the reference's scenes (common.frag:8-11): the plain
  * renders ignore them and rm_render_accumulate* reads them.  Other names warn
  * once on stderr and are ignored, as SFML does for uniforms the GLSL compiler
- * removed.  Wrong arity -> RM_ERR_INVALID_ARGUMENT. */
+ * removed.  Wrong arity -> RM_ERR_INVALID_ARGUMENT.
+ *
+ * They also set what the loaded scene declares itself (rm_load_scene), as
+ * setUniform sets any uniform of the loaded shader: 1f..4f a float / vec2 /
+ * vec3 / vec4, 1i an int or a bool (non-zero: true), fv the elements
+ * [0, count) of an array of `components`-float elements from tightly packed
+ * host floats (count = 1 also sets a non-array uniform of that many
+ * components).  A declared name set with another arity or type -- a float
+ * setter on an int, fv with more elements than declared -- or a name longer
+ * than 63 characters is RM_ERR_INVALID_ARGUMENT, with the declared type in
+ * rm_last_error.  The values are read by the next render or rm_scene_eval
+ * call and travel in that launch's kernel arguments: setting one afterwards
+ * does not reach work already enqueued. */
 rm_status rm_set_uniform1f(rm_ctx *ctx, const char *name, float x);
 rm_status rm_set_uniform2f(rm_ctx *ctx, const char *name, float x, float y);
 rm_status rm_set_uniform3f(rm_ctx *ctx, const char *name, float x, float y, float z);
+rm_status rm_set_uniform4f(rm_ctx *ctx, const char *name, float x, float y, float z, float w);
+rm_status rm_set_uniform1i(rm_ctx *ctx, const char *name, int32_t v);
+rm_status rm_set_uniformfv(rm_ctx *ctx, const char *name, int components, const float *v, int count);
+
+/* The uniforms the loaded scene declares, in declaration order (none for a
+ * built-in scene), and their current values.  rm_get_uniformfv writes a
+ * float-typed uniform's components (an array's elements tightly packed) into
+ * v[0, capacity) and their number into *written (may be NULL);
+ * rm_get_uniform1i reads an int or a bool.  An undeclared name, the other
+ * type or too small a capacity is RM_ERR_INVALID_ARGUMENT. */
+typedef enum rm_uniform_type { RM_UNIFORM_FLOAT = 0, RM_UNIFORM_INT = 1, RM_UNIFORM_BOOL = 2 } rm_uniform_type;
+typedef struct rm_uniform_info {
+    char name[64];   /* NUL-terminated                      */
+    int32_t type;    /* rm_uniform_type                     */
+    int32_t components; /* 1..4 (int, bool: 1)              */
+    int32_t count;   /* array length; 0: not an array       */
+} rm_uniform_info;
+rm_status rm_uniform_count(rm_ctx *ctx, int *n);
+rm_status rm_uniform_info_at(rm_ctx *ctx, int index, rm_uniform_info *out);
+rm_status rm_get_uniformfv(rm_ctx *ctx, const char *name, float *v, int capacity, int *written);
+rm_status rm_get_uniform1i(rm_ctx *ctx, const char *name, int32_t *v);
 
 rm_status rm_set_params(rm_ctx *ctx, const rm_params *params);
 rm_status rm_get_params(rm_ctx *ctx, rm_params *params);

@@ -33,6 +33,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -45,6 +46,7 @@ namespace rm {
 
 struct Vec2 { float x, y; };
 struct Vec3 { float x, y, z; };
+struct Vec4 { float x, y, z, w; };
 
 class Shader {
 public:
@@ -76,6 +78,25 @@ public:
     bool setUniform(const char* name, Vec3 v) {
         return ctx_ && rm_set_uniform3f(ctx_, name, v.x, v.y, v.z) == RM_OK;
     }
+    // uniforms the loaded scene declares itself (rm.h, rm_load_scene), as
+    // sf::Shader names the overloads: Glsl::Vec4, int, bool, and the arrays
+    bool setUniform(const char* name, Vec4 v) {
+        return ctx_ && rm_set_uniform4f(ctx_, name, v.x, v.y, v.z, v.w) == RM_OK;
+    }
+    bool setUniform(const char* name, int v) { return ctx_ && rm_set_uniform1i(ctx_, name, v) == RM_OK; }
+    bool setUniform(const char* name, bool v) { return ctx_ && rm_set_uniform1i(ctx_, name, v ? 1 : 0) == RM_OK; }
+    bool setUniformArray(const char* name, const float* v, std::size_t length) {
+        return setArray(name, 1, v, length);
+    }
+    bool setUniformArray(const char* name, const Vec2* v, std::size_t length) {
+        return setArray(name, 2, reinterpret_cast<const float*>(v), length);
+    }
+    bool setUniformArray(const char* name, const Vec3* v, std::size_t length) {
+        return setArray(name, 3, reinterpret_cast<const float*>(v), length);
+    }
+    bool setUniformArray(const char* name, const Vec4* v, std::size_t length) {
+        return setArray(name, 4, reinterpret_cast<const float*>(v), length);
+    }
     // The reference's compile-time MAX_MARCHING_STEPS (common.frag:15) and the
     // uncapped soft-shadow loop (common.frag:814) are run-time here.
     bool setMarchSteps(int max_steps, int shadow_max_steps = 0) {
@@ -87,9 +108,13 @@ public:
     }
 
 private:
+    bool setArray(const char* name, int components, const float* v, std::size_t length) {
+        return ctx_ && length <= 64 && rm_set_uniformfv(ctx_, name, components, v, (int)length) == RM_OK;
+    }
     rm_ctx* ctx_ = nullptr;
     int device_ = 0;
 };
+static_assert(sizeof(Vec2) == 8 && sizeof(Vec3) == 12 && sizeof(Vec4) == 16, "tightly packed floats (rm_set_uniformfv)");
 
 class RenderTexture;
 

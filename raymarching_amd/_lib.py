@@ -30,7 +30,9 @@ EXPORTS = ("rm_create", "rm_destroy", "rm_load_scene", "rm_set_uniform1f", "rm_s
            "rm_set_tile_order", "rm_tile_grid", "rm_comm_info", "rm_abi_version", "rm_cycle_rows",
            "rm_render_cycle_rows", "rm_render_cycle_rows_rgba8", "rm_deinterleave_cycle_rgb8",
            "rm_render_sharded_runs", "rm_render_sharded_runs_all", "rm_wire_capacity", "rm_wire_workspace_bytes",
-           "rm_wire_encode", "rm_wire_decode", "rm_scatter_part_rgba8", "rm_wire_decode_parts")
+           "rm_wire_encode", "rm_wire_decode", "rm_scatter_part_rgba8", "rm_wire_decode_parts",
+           "rm_set_uniform4f", "rm_set_uniform1i", "rm_set_uniformfv", "rm_uniform_count", "rm_uniform_info_at",
+           "rm_get_uniformfv", "rm_get_uniform1i")
 
 # include/rm.h RM_ABI_VERSION: the struct layouts below
 ABI_VERSION = 3
@@ -61,6 +63,14 @@ class RmStats(ctypes.Structure):
 class RmShardLayout(ctypes.Structure):
     _fields_ = [("rows_mine", ctypes.c_int32), ("rows_per_shard", ctypes.c_int32), ("wire_bytes", ctypes.c_int64),
                 ("gathered_bytes", ctypes.c_int64)]
+
+
+class RmUniformInfo(ctypes.Structure):
+    _fields_ = [("name", ctypes.c_char * 64), ("type", ctypes.c_int32), ("components", ctypes.c_int32),
+                ("count", ctypes.c_int32)]
+
+
+UNIFORM_TYPES = {0: "float", 1: "int", 2: "bool"}  # include/rm.h rm_uniform_type
 
 
 class RmCommId(ctypes.Structure):
@@ -100,6 +110,13 @@ def lib() -> ctypes.CDLL:
         "rm_set_uniform1f": ([vp, cp, c.c_float], c.c_int),
         "rm_set_uniform2f": ([vp, cp, c.c_float, c.c_float], c.c_int),
         "rm_set_uniform3f": ([vp, cp, c.c_float, c.c_float, c.c_float], c.c_int),
+        "rm_set_uniform4f": ([vp, cp, c.c_float, c.c_float, c.c_float, c.c_float], c.c_int),
+        "rm_set_uniform1i": ([vp, cp, c.c_int32], c.c_int),
+        "rm_set_uniformfv": ([vp, cp, c.c_int, vp, c.c_int], c.c_int),
+        "rm_uniform_count": ([vp, c.POINTER(c.c_int)], c.c_int),
+        "rm_uniform_info_at": ([vp, c.c_int, c.POINTER(RmUniformInfo)], c.c_int),
+        "rm_get_uniformfv": ([vp, cp, vp, c.c_int, c.POINTER(c.c_int)], c.c_int),
+        "rm_get_uniform1i": ([vp, cp, c.POINTER(c.c_int32)], c.c_int),
         "rm_set_params": ([vp, c.POINTER(RmParams)], c.c_int),
         "rm_get_params": ([vp, c.POINTER(RmParams)], c.c_int),
         "rm_set_stream": ([vp, vp], c.c_int),

@@ -41,6 +41,7 @@ class Renderer:
         if st != 0:
             raise _lib.RmError(st, f"rm_create(device={device}) failed")
         self.device = int(device)
+        self._uniform_types = {}  # of the loaded scene's own uniforms: name -> "float" | "int" | "bool"
 
     def close(self):
         if self._ctx:
@@ -56,19 +57,73 @@ class Renderer:
     # --- state ---------------------------------------------------------
     def load_scene(self, name: str) -> None:
         check(lib().rm_load_scene(self._ctx, name.encode()), self._ctx)
+        self._uniform_types = {u.name.decode(): _lib.UNIFORM_TYPES[u.type] for u in self._uniform_infos()}
 
-    def set_uniform(self, name: str, *v: float) -> None:
+    def set_uniform(self, name: str, *v) -> None:
+        """rm_set_uniform{1,2,3,4}f; a uniform the loaded scene declares as
+        int or bool goes through rm_set_uniform1i."""
         L = lib()
         n = name.encode()
-        if len(v) == 1:
+        if len(v) == 1 and self._uniform_types.get(name) in ("int", "bool"):
+            st = L.rm_set_uniform1i(self._ctx, n, int(v[0]))
+        elif len(v) == 1:
             st = L.rm_set_uniform1f(self._ctx, n, float(v[0]))
         elif len(v) == 2:
             st = L.rm_set_uniform2f(self._ctx, n, float(v[0]), float(v[1]))
         elif len(v) == 3:
             st = L.rm_set_uniform3f(self._ctx, n, float(v[0]), float(v[1]), float(v[2]))
+        elif len(v) == 4:
+            st = L.rm_set_uniform4f(self._ctx, n, float(v[0]), float(v[1]), float(v[2]), float(v[3]))
         else:
-            raise ValueError("uniforms have 1..3 float components")
+            raise ValueError("uniforms have 1..4 components")
         check(st, self._ctx)
+
+    def set_uniform_array(self, name: str, array) -> None:
+        """rm_set_uniformfv: elements [0, len(array)) of an array uniform from a
+        [count] (float elements) or [count, components] array."""
+        import numpy as np
+        a = np.ascontiguousarray(array, np.float32)
+        if a.ndim == 1:
+            a = a.reshape(-1, 1)
+        if a.ndim != 2 or a.shape[0] < 1 or not 1 <= a.shape[1] <= 4:
+            raise ValueError("set_uniform_array: a [count] or [count, 1..4] array of floats")
+        check(lib().rm_set_uniformfv(self._ctx, name.encode(), int(a.shape[1]), ctypes.c_void_p(a.ctypes.data),
+                                     int(a.shape[0])), self._ctx)
+
+    def _uniform_infos(self):
+        n = ctypes.c_int()
+        check(lib().rm_uniform_count(self._ctx, ctypes.byref(n)), self._ctx)
+        infos = []
+        for i in range(n.value):
+            u = _lib.RmUniformInfo()
+            check(lib().rm_uniform_info_at(self._ctx, i, ctypes.byref(u)), self._ctx)
+            infos.append(u)
+        return infos
+
+    def uniforms(self) -> dict:
+        """The uniforms the loaded scene declares, in declaration order:
+        {name: dict(type, components, count, value)} with type "float", "int"
+        or "bool", count 0 for a non-array, and value a float / int / bool, a
+        tuple of floats (vec2..vec4), or a [count, components] float32 array
+        ([count] for an array of floats)."""
+        import numpy as np
+        out = {}
+        for u in self._uniform_infos():
+            name, ty = u.name.decode(), _lib.UNIFORM_TYPES[u.type]
+            if ty == "float":
+                v = np.zeros(u.components * max(1, u.count), np.float32)
+                check(lib().rm_get_uniformfv(self._ctx, u.name, ctypes.c_void_p(v.ctypes.data), len(v), None),
+                      self._ctx)
+                if u.count:
+                    value = v.reshape(u.count, u.components) if u.components > 1 else v
+                else:
+                    value = float(v[0]) if u.components == 1 else tuple(float(x) for x in v)
+            else:
+                i = ctypes.c_int32()
+                check(lib().rm_get_uniform1i(self._ctx, u.name, ctypes.byref(i)), self._ctx)
+                value = bool(i.value) if ty == "bool" else int(i.value)
+            out[name] = dict(type=ty, components=int(u.components), count=int(u.count), value=value)
+        return out
 
     def set_pose(self, pos, mouse, time) -> None:
         self.set_uniform("u_pos", *pos)

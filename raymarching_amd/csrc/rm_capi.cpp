@@ -116,6 +116,7 @@ rm_status rm_load_scene(rm_ctx *ctx, const char *file_name) {
     std::ifstream probe(file);
     bool exists = probe.is_open();
     probe.close();
+    rmuniform::Table uniforms;  // what the scene declares (a built-in scene: none)
     if (exists) {
         std::string src, err;
         rm_status st = rmscene::load_scene_file(file, sc, src, err);
@@ -128,14 +129,14 @@ rm_status rm_load_scene(rm_ctx *ctx, const char *file_name) {
             // failure the previous scene stays loaded
             rmplugin::Code code;
             std::string log;
-            if (!rmplugin::compile(src, file, code, log)) {
+            if (!rmplugin::compile(src, file, code, log, uniforms)) {
                 std::fprintf(stderr, "%s\n", log.c_str());
                 return fail(ctx, RM_ERR_SCENE, "scene plugin \"" + file + "\" failed to compile:\n" + log);
             }
             RM_HIP(hipSetDevice(ctx->device));
             // kernels of the previous code object may still run on the stream
             RM_HIP(hipStreamSynchronize(ctx->stream));
-            hipError_t e = rmplugin::load(code, ctx->plugin);
+            hipError_t e = rmplugin::load(code, uniforms.slots, ctx->plugin);
             if (e != hipSuccess) return hip_fail(ctx, e, "scene plugin module load");
         }
     } else if (sc < 0) {
@@ -145,20 +146,49 @@ rm_status rm_load_scene(rm_ctx *ctx, const char *file_name) {
     }
     ctx->scene = sc;
     ctx->scene_file = file;
+    // a loaded scene starts from its declarations' defaults, as a fresh GL
+    // program does (the reference's reload makes a new program)
+    uniforms.defaults(ctx->uniform_values);
+    ctx->uniforms = std::move(uniforms);
     ctx->err.clear();
     return RM_OK;
 }
 
-static rm_status set_uniform(rm_ctx *ctx, const char *name, int n, float x, float y, float z) {
+// The seven uniforms of the pass (common.frag:4-11), then the ones the loaded
+// scene declares; any other name warns once and is ignored.
+struct PassUniform { const char *name; int n; };
+static const PassUniform kPassUniforms[] = {{"u_resolution", 2}, {"u_pos", 3}, {"u_mouse", 2}, {"u_time", 1},
+                                            {"u_sample_part", 1}, {"u_seed1", 2}, {"u_seed2", 2}};
+
+static rm_status warn_unknown(rm_ctx *ctx, const char *name) {
+    if (ctx->warned.insert(name).second) std::fprintf(stderr, "rm: uniform \"%s\" not found in shader\n", name);
+    return RM_OK;
+}
+
+static rm_status long_name(rm_ctx *ctx, const char *name) {
+    return fail(ctx, RM_ERR_INVALID_ARGUMENT, "uniform name of " + std::to_string(std::strlen(name)) +
+                                                  " characters (at most " + std::to_string(rmuniform::kMaxName) + ")");
+}
+
+static rm_status wrong_type(rm_ctx *ctx, const rmuniform::Decl &d, const std::string &got) {
+    return fail(ctx, RM_ERR_INVALID_ARGUMENT,
+                "uniform \"" + d.name + "\" is declared " + rmuniform::type_name(d) + ", got " + got);
+}
+
+static std::string floats_name(int n, int count = 1) {
+    return (n == 1 ? std::string("float") : "vec" + std::to_string(n)) +
+           (count > 1 ? "[" + std::to_string(count) + "]" : std::string());
+}
+
+static rm_status set_uniform(rm_ctx *ctx, const char *name, int n, float x, float y, float z, float w = 0.0f) {
     if (!ctx || !name) return RM_ERR_INVALID_ARGUMENT;
+    if (std::strlen(name) > (size_t)rmuniform::kMaxName) return long_name(ctx, name);
     std::string nm(name);
-    struct U { const char *name; int n; };
-    static const U known[] = {{"u_resolution", 2}, {"u_pos", 3}, {"u_mouse", 2}, {"u_time", 1},
-                              {"u_sample_part", 1}, {"u_seed1", 2}, {"u_seed2", 2}};
-    for (const U &u : known) {
+    for (const PassUniform &u : kPassUniforms) {
         if (nm != u.name) continue;
         if (n != u.n) return fail(ctx, RM_ERR_INVALID_ARGUMENT, "uniform \"" + nm + "\" has " + std::to_string(u.n) +
-                                                                    " components, got " + std::to_string(n));
+                                                                    " components, got " +
+                                                                    (n ? std::to_string(n) : std::string("an int")));
         if (nm == "u_resolution") { ctx->res[0] = x; ctx->res[1] = y; ctx->res_set = true; }
         else if (nm == "u_pos") { ctx->pos[0] = x; ctx->pos[1] = y; ctx->pos[2] = z; }
         else if (nm == "u_mouse") { ctx->mouse[0] = x; ctx->mouse[1] = y; }
@@ -170,8 +200,13 @@ static rm_status set_uniform(rm_ctx *ctx, const char *name, int n, float x, floa
         else if (nm == "u_seed2") { ctx->seed2[0] = x; ctx->seed2[1] = y; }
         return RM_OK;
     }
-    if (ctx->warned.insert(nm).second) std::fprintf(stderr, "rm: uniform \"%s\" not found in shader\n", name);
-    return RM_OK;
+    if (const rmuniform::Decl *d = ctx->uniforms.find(nm)) {
+        if (d->type != rmuniform::kFloat || d->count || d->components != n) return wrong_type(ctx, *d, floats_name(n));
+        const float v[4] = {x, y, z, w};
+        std::memcpy(ctx->uniform_values + 4 * d->slot, v, (size_t)n * sizeof(float));
+        return RM_OK;
+    }
+    return warn_unknown(ctx, name);
 }
 
 rm_status rm_set_uniform1f(rm_ctx *ctx, const char *name, float x) { return set_uniform(ctx, name, 1, x, 0, 0); }
@@ -181,6 +216,90 @@ rm_status rm_set_uniform2f(rm_ctx *ctx, const char *name, float x, float y) {
 rm_status rm_set_uniform3f(rm_ctx *ctx, const char *name, float x, float y, float z) {
     return set_uniform(ctx, name, 3, x, y, z);
 }
+rm_status rm_set_uniform4f(rm_ctx *ctx, const char *name, float x, float y, float z, float w) {
+    return set_uniform(ctx, name, 4, x, y, z, w);
+}
+
+rm_status rm_set_uniform1i(rm_ctx *ctx, const char *name, int32_t v) {
+    if (!ctx || !name) return RM_ERR_INVALID_ARGUMENT;
+    if (std::strlen(name) > (size_t)rmuniform::kMaxName) return long_name(ctx, name);
+    if (const rmuniform::Decl *d = ctx->uniforms.find(name)) {
+        if (d->type == rmuniform::kFloat) return wrong_type(ctx, *d, "int");
+        ctx->uniform_values[4 * d->slot] = d->type == rmuniform::kBool ? (uint32_t)(v != 0) : (uint32_t)v;
+        return RM_OK;
+    }
+    return set_uniform(ctx, name, 0, 0, 0, 0);  // a float uniform of the pass (refused), or an unknown name
+}
+
+rm_status rm_set_uniformfv(rm_ctx *ctx, const char *name, int components, const float *v, int count) {
+    if (!ctx || !name) return RM_ERR_INVALID_ARGUMENT;
+    if (!v || components < 1 || components > 4 || count < 1)
+        return fail(ctx, RM_ERR_INVALID_ARGUMENT, "rm_set_uniformfv: bad arguments");
+    if (std::strlen(name) > (size_t)rmuniform::kMaxName) return long_name(ctx, name);
+    const rmuniform::Decl *d = ctx->uniforms.find(name);
+    if (!d || !d->count) {  // not an array: the plain setter of that arity, for one element
+        if (count == 1) return set_uniform(ctx, name, components, v[0], components > 1 ? v[1] : 0.0f,
+                                           components > 2 ? v[2] : 0.0f, components > 3 ? v[3] : 0.0f);
+        if (d) return wrong_type(ctx, *d, floats_name(components, count));
+        for (const PassUniform &u : kPassUniforms)
+            if (std::strcmp(name, u.name) == 0)
+                return fail(ctx, RM_ERR_INVALID_ARGUMENT, std::string("uniform \"") + name + "\" is not an array");
+        return warn_unknown(ctx, name);
+    }
+    if (d->components != components || count > d->count) return wrong_type(ctx, *d, floats_name(components, count));
+    for (int i = 0; i < count; i++)
+        std::memcpy(ctx->uniform_values + 4 * (d->slot + i), v + (size_t)i * components, (size_t)components * sizeof(float));
+    return RM_OK;
+}
+
+rm_status rm_uniform_count(rm_ctx *ctx, int *n) {
+    if (!ctx || !n) return RM_ERR_INVALID_ARGUMENT;
+    *n = (int)ctx->uniforms.decls.size();
+    return RM_OK;
+}
+
+rm_status rm_uniform_info_at(rm_ctx *ctx, int index, rm_uniform_info *out) {
+    if (!ctx || !out) return RM_ERR_INVALID_ARGUMENT;
+    if (index < 0 || index >= (int)ctx->uniforms.decls.size())
+        return fail(ctx, RM_ERR_INVALID_ARGUMENT, "rm_uniform_info_at: index outside [0, rm_uniform_count)");
+    const rmuniform::Decl &d = ctx->uniforms.decls[(size_t)index];
+    static_assert(sizeof(out->name) == rmuniform::kMaxName + 1, "rm_uniform_info.name");
+    std::memset(out, 0, sizeof(*out));
+    std::memcpy(out->name, d.name.c_str(), d.name.size());
+    out->type = d.type;
+    out->components = d.components;
+    out->count = d.count;
+    return RM_OK;
+}
+
+rm_status rm_get_uniformfv(rm_ctx *ctx, const char *name, float *v, int capacity, int *written) {
+    if (!ctx || !name || !v) return RM_ERR_INVALID_ARGUMENT;
+    const rmuniform::Decl *d = ctx->uniforms.find(name);
+    if (!d) return fail(ctx, RM_ERR_INVALID_ARGUMENT, std::string("the loaded scene declares no uniform \"") + name + "\"");
+    if (d->type != rmuniform::kFloat) return wrong_type(ctx, *d, "a read of floats");
+    const int n = d->components * d->slots();
+    if (capacity < n)
+        return fail(ctx, RM_ERR_INVALID_ARGUMENT, "uniform \"" + d->name + "\" (" + rmuniform::type_name(*d) + ") has " +
+                                                      std::to_string(n) + " floats, capacity " + std::to_string(capacity));
+    for (int i = 0; i < d->slots(); i++)
+        std::memcpy(v + (size_t)i * d->components, ctx->uniform_values + 4 * (d->slot + i),
+                    (size_t)d->components * sizeof(float));
+    if (written) *written = n;
+    return RM_OK;
+}
+
+rm_status rm_get_uniform1i(rm_ctx *ctx, const char *name, int32_t *v) {
+    if (!ctx || !name || !v) return RM_ERR_INVALID_ARGUMENT;
+    const rmuniform::Decl *d = ctx->uniforms.find(name);
+    if (!d) return fail(ctx, RM_ERR_INVALID_ARGUMENT, std::string("the loaded scene declares no uniform \"") + name + "\"");
+    if (d->type == rmuniform::kFloat) return wrong_type(ctx, *d, "a read of an int");
+    *v = (int32_t)ctx->uniform_values[4 * d->slot];
+    return RM_OK;
+}
+
+static_assert((int)RM_UNIFORM_FLOAT == (int)rmuniform::kFloat && (int)RM_UNIFORM_INT == (int)rmuniform::kInt &&
+                  (int)RM_UNIFORM_BOOL == (int)rmuniform::kBool,
+              "rm_uniform_type and rm_uniform_decl.h");
 
 rm_status rm_set_params(rm_ctx *ctx, const rm_params *p) {
     if (!ctx || !p) return RM_ERR_INVALID_ARGUMENT;
@@ -656,7 +775,7 @@ rm_status rm_scene_eval(rm_ctx *ctx, const float *points, int64_t n, float *dist
     if (!dp) e = hipMemcpyAsync(const_cast<float *>(p), points, pb, hipMemcpyHostToDevice, ctx->stream);
     FrameConst F = frame_const(ctx, 1, 1, RowPart{1, 0, 1}, 1);
     if (e == hipSuccess)
-        e = ctx->scene == rm::SCENE_PLUGIN ? rmplugin::launch_eval(ctx->plugin, F, p, n, d, m, ctx->stream)
+        e = ctx->scene == rm::SCENE_PLUGIN ? rmplugin::launch_eval(ctx->plugin, F, ctx->uniform_values, p, n, d, m, ctx->stream)
                                            : rm::launch_scene_eval(ctx->scene, F, p, n, d, m, ctx->stream);
     if (e == hipSuccess && !dd) e = hipMemcpyAsync(dist, d, db, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess && material && !dm) e = hipMemcpyAsync(material, m, mb, hipMemcpyDeviceToHost, ctx->stream);
@@ -677,7 +796,8 @@ rm_status rm_compile_scene(const char *file_name, char *log, size_t log_size) {
         clog = "compiled-in scene " + std::string(sc == rm::SCENE_T ? "T" : sc == rm::SCENE_O ? "O" : "(built-in)");
     } else {
         rmplugin::Code code;
-        if (!rmplugin::compile(src, file_name, code, clog)) st = RM_ERR_SCENE;
+        rmuniform::Table uniforms;
+        if (!rmplugin::compile(src, file_name, code, clog, uniforms)) st = RM_ERR_SCENE;
     }
     if (log && log_size > 0) {
         size_t k = clog.size() < log_size - 1 ? clog.size() : log_size - 1;

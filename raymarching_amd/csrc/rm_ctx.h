@@ -74,6 +74,11 @@ struct rm_ctx {
     hipStream_t bloom_stream = nullptr;
     bool bloom_pending = false;  // a bloom ran on bloom_stream since bloom_ev was last recorded
     rmplugin::Module plugin;  // the loaded scene plugin (scene == SCENE_PLUGIN)
+    // the uniforms the loaded scene declares itself (empty for a built-in
+    // scene) and their current values, the block every plugin launch passes by
+    // value; a successful rm_load_scene sets the declarations' defaults
+    rmuniform::Table uniforms;
+    uint32_t uniform_values[rmuniform::kBlockWords] = {};
     uint32_t *tile_order = nullptr;  // rm_set_tile_order (device copy)
     int64_t tile_order_n = 0;
     // adaptive dispatch order (rm_params.schedule): per launch geometry and

@@ -13,7 +13,10 @@
 // The scene source defines `SdResult sceneSDF(vec3 p)` with the library of
 // rm_sdf_lib.h, as output_shader.frag:12-48 does with common.frag, and may
 // read the pass's uniforms u_resolution, u_pos, u_mouse, u_time
-// (common.frag:4-7).  The render pipeline is output_shader.frag's render()
+// (common.frag:4-7), and uniforms it declares itself (`uniform vec4 u_ball =
+// ...;`, rm_uniform_decl.h: the translation unit then starts with
+// #define RM_UNIFORM_SLOTS n and wraps the scene in one #define per name, see
+// UniformBlock below).  The render pipeline is output_shader.frag's render()
 // and main() (rm_render_direct.h render_O), as for the compiled-in scene O.
 #pragma once
 #include "rm_render_direct.h"
@@ -36,6 +39,67 @@ typedef const __attribute__((address_space(4))) FrameConst* KernargFrame;
 __device__ __forceinline__ KernargFrame plugin_frame() {
     return (KernargFrame)__builtin_amdgcn_kernarg_segment_ptr();
 }
+
+#ifdef RM_UNIFORM_SLOTS
+// The uniforms a scene declares itself (`uniform vec4 u_ball = ...;`,
+// rm_uniform_decl.h): RM_UNIFORM_SLOTS slots of 16 bytes, the second argument
+// of every kernel of such a scene (rm_plugin_kernels.h), read like the
+// FrameConst before it: from the kernel-argument segment, in the constant
+// address space, at an offset fixed here.  A scene without declarations
+// defines no RM_UNIFORM_SLOTS and has the kernels it always had.
+struct alignas(16) UniformBlock {
+    uint32_t w[4 * RM_UNIFORM_SLOTS];
+};
+struct PluginArgsHead {  // the kernels' first two parameters, as the kernel-argument segment lays them out
+    FrameConst F;
+    UniformBlock U;
+};
+constexpr int kUniformOffset = (int)((sizeof(FrameConst) + 15) & ~(size_t)15);
+static_assert(__builtin_offsetof(PluginArgsHead, U) == kUniformOffset && alignof(FrameConst) <= 16,
+              "the uniform block follows the FrameConst in the kernel-argument segment");
+static_assert(RM_UNIFORM_SLOTS >= 1 && RM_UNIFORM_SLOTS <= 64, "rm_uniform_decl.h kMaxSlots");
+
+typedef const __attribute__((address_space(4))) char* KernargBytes;
+__device__ __forceinline__ float uniform_f(int byte) {
+    return *(const __attribute__((address_space(4))) float*)((KernargBytes)__builtin_amdgcn_kernarg_segment_ptr() +
+                                                             kUniformOffset + byte);
+}
+__device__ __forceinline__ int uniform_i(int byte) {
+    return *(const __attribute__((address_space(4))) int*)((KernargBytes)__builtin_amdgcn_kernarg_segment_ptr() +
+                                                           kUniformOffset + byte);
+}
+// a float / vec2 / vec3 / vec4 (of either library instance) at a byte offset of the block
+template <class V>
+__device__ __forceinline__ V uniform_v(int byte) {
+    if constexpr (sizeof(V) == 4) return uniform_f(byte);
+    else if constexpr (sizeof(V) == 8) return V(uniform_f(byte), uniform_f(byte + 4));
+    else if constexpr (sizeof(V) == 12) return V(uniform_f(byte), uniform_f(byte + 4), uniform_f(byte + 8));
+    else return V(uniform_f(byte), uniform_f(byte + 4), uniform_f(byte + 8), uniform_f(byte + 12));
+}
+// `name[i]` of an array uniform, i any int: wave-uniform indices are scalar
+// loads, others vector loads of the same constant memory.  (GLSL leaves an
+// index outside [0, N) undefined; here it reads the nearest element, never
+// outside the block.)
+template <class V, int BYTE, int N>
+struct UniformArray {
+    __device__ __forceinline__ V operator[](int i) const {
+        const int k = i < 0 ? 0 : i > N - 1 ? N - 1 : i;
+        return uniform_v<V>(BYTE + 16 * k);
+    }
+};
+// N words of the block, loaded at the top of a kernel and kept by an empty
+// asm: the reads of the same words inside the march loops are then copies of
+// these loads, and what depends on them alone -- transformR's sin and cos of
+// u_time * u_spin -- leaves the loops (without it LLVM kept
+// the scalar loads and everything computed from them in every loop body)
+template <int BYTE, int N>
+__device__ __forceinline__ void uniform_keep() {
+    if constexpr (N >= 1) asm volatile("" ::"s"(uniform_f(BYTE)));
+    if constexpr (N >= 2) asm volatile("" ::"s"(uniform_f(BYTE + 4)));
+    if constexpr (N >= 3) asm volatile("" ::"s"(uniform_f(BYTE + 8)));
+    if constexpr (N >= 4) asm volatile("" ::"s"(uniform_f(BYTE + 12)));
+}
+#endif
 
 }  // namespace glsl
 }  // namespace rm

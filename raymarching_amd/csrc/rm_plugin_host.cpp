@@ -186,7 +186,7 @@ namespace {
 std::mutex g_mu;
 std::map<std::string, Code> g_cache;
 
-std::string translation_unit(const std::string& src, const std::string& file) {
+std::string translation_unit(const std::string& src, const std::string& file, const rmuniform::Table& uniforms) {
     std::string name;
     for (char c : file) {
         if (c == '"' || c == '\\') name += '\\';
@@ -208,19 +208,30 @@ std::string translation_unit(const std::string& src, const std::string& file) {
                "\n#pragma clang attribute pop\n"
                "#pragma clang force_cuda_host_device end\n" + post + "}  // namespace\n" + close;
     };
-    return "#include \"rm_plugin.h\"\n" +
+    // the scene's own uniforms (rm_uniform_decl.h): each name reads its slot of
+    // the kernels' uniform block, in both instances; a scene without any has
+    // the text, and so the code object, it had before there were such uniforms
+    std::string head, defines, undefs;
+    if (!uniforms.decls.empty()) {
+        head = "#define RM_UNIFORM_SLOTS " + std::to_string(uniforms.slots) + "\n";
+        rmuniform::device_text(uniforms, defines, undefs);
+    }
+    return head + "#include \"rm_plugin.h\"\n" + defines +
            instance("namespace rm {\nnamespace glsl {\n", "}  // namespace glsl\n}  // namespace rm\n", "", "") +
            instance("namespace rm {\nnamespace glsl {\nnamespace probe {\n",
                     "}  // namespace probe\n}  // namespace glsl\n}  // namespace rm\n",
                     "#pragma clang fp contract(fast)\n#if RM_PROBE_REASSOC\n#pragma clang fp reassociate(on)\n#endif\n",
                     "#if RM_PROBE_REASSOC\n#pragma clang fp reassociate(off)\n#endif\n#pragma clang fp contract(off)\n") +
-           "#include \"rm_plugin_kernels.h\"\n";
+           undefs + "#include \"rm_plugin_kernels.h\"\n";
 }
 
 }  // namespace
 
-bool compile(const std::string& src, const std::string& file, Code& code, std::string& log) {
-    const std::string tu = translation_unit(src, file);
+bool compile(const std::string& src, const std::string& file, Code& code, std::string& log,
+             rmuniform::Table& uniforms) {
+    std::string scene;
+    if (!rmuniform::parse(src, file, uniforms, scene, log)) return false;
+    const std::string tu = translation_unit(scene, file, uniforms);
     log.clear();
     {
         std::lock_guard<std::mutex> g(g_mu);
@@ -270,7 +281,7 @@ bool compile(const std::string& src, const std::string& file, Code& code, std::s
     return true;
 }
 
-hipError_t load(const Code& code, Module& m) {
+hipError_t load(const Code& code, int uniform_slots, Module& m) {
     Module n;
     hipError_t e = hipModuleLoadData(&n.mod, code->data());
     if (e != hipSuccess) return e;
@@ -285,6 +296,7 @@ hipError_t load(const Code& code, Module& m) {
         return e;
     }
     n.code = code;
+    n.uniform_slots = uniform_slots;
     unload(m);
     m = n;
     return hipSuccess;
@@ -295,29 +307,36 @@ void unload(Module& m) {
     m = Module();
 }
 
-hipError_t launch_render(const Module& m, const rm::FrameConst& F, void* out, bool rgba8, unsigned long long* evals,
-                         hipStream_t s) {
+hipError_t launch_render(const Module& m, const rm::FrameConst& F, const uint32_t* uniforms, void* out, bool rgba8,
+                         unsigned long long* evals, hipStream_t s) {
     if (!m.render || !m.render_count) return hipErrorInvalidDeviceFunction;
     rm::FrameConst f = F;
     f.gx_magic = rm::div_magic((uint32_t)((F.W + 7) / 8), (uint64_t)((F.W + 7) / 8) * (uint64_t)((F.nrows + 7) / 8));
     void* o = out;
     int r8 = rgba8 ? 1 : 0;
     unsigned long long* e = evals;
+    // (the launch copies each argument by the size the kernel declares: the
+    // block's first uniform_slots slots, read now -- a later rm_set_uniform*
+    // does not reach a launch already enqueued)
+    void* with_block[] = {&f, const_cast<uint32_t*>(uniforms), &o, &r8, &e};
     void* args[] = {&f, &o, &r8, &e};
     return hipModuleLaunchKernel(evals ? m.render_count : m.render, (unsigned)((F.W + 7) / 8),
-                                 (unsigned)((F.nrows + 7) / 8), 1, 64, 1, 1, 0, s, args, nullptr);
+                                 (unsigned)((F.nrows + 7) / 8), 1, 64, 1, 1, 0, s,
+                                 m.uniform_slots > 0 ? with_block : args, nullptr);
 }
 
-hipError_t launch_eval(const Module& m, const rm::FrameConst& F, const float* pts, long long n, float* dist,
-                       float* mat, hipStream_t s) {
+hipError_t launch_eval(const Module& m, const rm::FrameConst& F, const uint32_t* uniforms, const float* pts,
+                       long long n, float* dist, float* mat, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     rm::FrameConst f = F;
     const float* p = pts;
     long long nn = n;
     float* d = dist;
     float* mm = mat;
+    void* with_block[] = {&f, const_cast<uint32_t*>(uniforms), &p, &nn, &d, &mm};
     void* args[] = {&f, &p, &nn, &d, &mm};
-    return hipModuleLaunchKernel(m.eval, (unsigned)((n + 255) / 256), 1, 1, 256, 1, 1, 0, s, args, nullptr);
+    return hipModuleLaunchKernel(m.eval, (unsigned)((n + 255) / 256), 1, 1, 256, 1, 1, 0, s,
+                                 m.uniform_slots > 0 ? with_block : args, nullptr);
 }
 
 }  // namespace rmplugin

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "rm_device.h"
+#include "rm_uniform_decl.h"
 
 namespace rmplugin {
 
@@ -22,9 +23,14 @@ using Code = std::shared_ptr<const std::vector<char>>;
 // swz2/swz3/swz4<indices>(e).  Swizzle writes are not translated.
 std::string glsl_source(const std::string& src);
 
-// Compile a (preprocessed) scene source; code objects are cached by source
-// text.  On failure `log` holds the compiler's diagnostics.
-bool compile(const std::string& src, const std::string& file, Code& code, std::string& log);
+// Compile a (preprocessed) scene source; code objects are cached by the text
+// handed to the compiler.  `uniforms` receives the scene's `uniform`
+// declarations (rm_uniform_decl.h), read from `src` on every call: the
+// compiler sees the source with the declarations blanked, so two sources that
+// differ in a default value share a code object and nothing else.  On failure
+// `log` holds the diagnostics.
+bool compile(const std::string& src, const std::string& file, Code& code, std::string& log,
+             rmuniform::Table& uniforms);
 
 struct Module {
     hipModule_t mod = nullptr;
@@ -32,12 +38,16 @@ struct Module {
     hipFunction_t render_count = nullptr;  // instrumented render kernel (ray-step counts, step maps)
     hipFunction_t eval = nullptr;
     Code code;
+    int uniform_slots = 0;  // > 0: the kernels take the uniform block as their second argument (rm_plugin.h)
 };
-hipError_t load(const Code& code, Module& m);  // on the current device; m keeps its old module on failure
+// on the current device; m keeps its old module on failure
+hipError_t load(const Code& code, int uniform_slots, Module& m);
 void unload(Module& m);
-hipError_t launch_render(const Module& m, const rm::FrameConst& F, void* out, bool rgba8, unsigned long long* evals,
-                         hipStream_t s);
-hipError_t launch_eval(const Module& m, const rm::FrameConst& F, const float* pts, long long n, float* dist,
-                       float* mat, hipStream_t s);
+// `uniforms`: the context's block of rmuniform::kBlockWords words, copied into
+// the kernel arguments by the launch call (its first m.uniform_slots slots)
+hipError_t launch_render(const Module& m, const rm::FrameConst& F, const uint32_t* uniforms, void* out, bool rgba8,
+                         unsigned long long* evals, hipStream_t s);
+hipError_t launch_eval(const Module& m, const rm::FrameConst& F, const uint32_t* uniforms, const float* pts,
+                       long long n, float* dist, float* mat, hipStream_t s);
 
 }  // namespace rmplugin

@@ -1,8 +1,18 @@
 // rm_plugin_kernels.h -- epilogue of a scene plugin's translation unit
 // (rm_plugin.h): binds the scene's sceneSDF to the render pipeline and defines
 // the plugin's kernels, looked up by name (rm_plugin_host.cpp).  The first
-// argument of every kernel is the FrameConst the uniforms are bound from.
+// argument of every kernel is the FrameConst the uniforms are bound from; a
+// scene that declares uniforms of its own has their block as the second
+// (rm_plugin.h UniformBlock: read from the kernel-argument segment, so the
+// parameter itself is never named), loaded once at the top of each kernel.
 #pragma once
+
+#ifdef RM_UNIFORM_SLOTS
+#define RM_UNIFORM_PARAM rm::glsl::UniformBlock,
+#else
+#define RM_UNIFORM_PARAM
+#define RM_UNIFORM_PRELOAD()
+#endif
 
 template <>
 struct rm::PluginScene<rm::SCENE_PLUGIN> {
@@ -57,18 +67,21 @@ __device__ __forceinline__ void plugin_render_tile(const FrameConst& F, void* ou
     if constexpr (COUNT) store_tally(F, evals, cnt, x, j, lane);
 }
 }  // namespace rm
-extern "C" __global__ __launch_bounds__(64) void rm_plugin_render(rm::FrameConst F, void* out, int rgba8,
-                                                                  unsigned long long* evals) {
+extern "C" __global__ __launch_bounds__(64) void rm_plugin_render(rm::FrameConst F, RM_UNIFORM_PARAM void* out,
+                                                                  int rgba8, unsigned long long* evals) {
+    RM_UNIFORM_PRELOAD();
     rm::plugin_render_tile<false>(F, out, rgba8, evals);
 }
-extern "C" __global__ __launch_bounds__(64) void rm_plugin_render_count(rm::FrameConst F, void* out, int rgba8,
-                                                                         unsigned long long* evals) {
+extern "C" __global__ __launch_bounds__(64) void rm_plugin_render_count(rm::FrameConst F, RM_UNIFORM_PARAM void* out,
+                                                                         int rgba8, unsigned long long* evals) {
+    RM_UNIFORM_PRELOAD();
     rm::plugin_render_tile<true>(F, out, rgba8, evals);
 }
 #endif
 
 // sceneSDF(p) at explicit points (rm_scene_eval)
-extern "C" __global__ __launch_bounds__(256) void rm_plugin_eval(rm::FrameConst F, const float* pts, long long n,
-                                                                 float* dist, float* mat) {
+extern "C" __global__ __launch_bounds__(256) void rm_plugin_eval(rm::FrameConst F, RM_UNIFORM_PARAM const float* pts,
+                                                                 long long n, float* dist, float* mat) {
+    RM_UNIFORM_PRELOAD();
     rm::scene_eval_one<rm::SCENE_PLUGIN>(F, pts, n, dist, mat);
 }

@@ -186,7 +186,7 @@ rm_status render_dev(rm_ctx *ctx, int W, int H, const RowPart &part, int row0, i
         wire ? rm::launch_render_wire(ctx->scene, F, static_cast<rm::WireTile *>(out), cnt ? ctx->d_evals : nullptr,
                                       ctx->stream)
         : ctx->scene == rm::SCENE_PLUGIN
-            ? rmplugin::launch_render(ctx->plugin, F, out, rgba8, cnt ? ctx->d_evals : nullptr, ctx->stream)
+            ? rmplugin::launch_render(ctx->plugin, F, ctx->uniform_values, out, rgba8, cnt ? ctx->d_evals : nullptr, ctx->stream)
             : rm::launch_render(ctx->scene, F, out, rgba8, cnt ? ctx->d_evals : nullptr, kernel, ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "render kernel launch");
     if (stats) RM_HIP(hipEventRecord(ctx->ev1, ctx->stream));

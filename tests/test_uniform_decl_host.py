@@ -1,0 +1,34 @@
+"""The parser of a scene's `uniform` declarations (csrc/rm_uniform_decl.cpp) on
+the CPU: tests/host/uniform_decl_test.cpp, a stand-alone program built with the
+host compiler under the address and undefined-behaviour sanitizers, as
+tests/test_host_logic.py builds its program, and linked with
+rm_uniform_decl.cpp only (nothing is loaded into Python).  No GPU."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SOURCES = [os.path.join(ROOT, "tests", "host", "uniform_decl_test.cpp"),
+           os.path.join(ROOT, "raymarching_amd", "csrc", "rm_uniform_decl.cpp")]
+FLAGS = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+
+
+def _compiler():
+    if shutil.which("g++"):  # (gcc's sanitizer runtimes are shared by default: link them in, as clang does)
+        return ["g++", "-static-libasan", "-static-libubsan"]
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    return [hipcc, "-x", "c++"] if os.path.exists(hipcc) else None
+
+
+def test_uniform_declarations_under_sanitizers(tmp_path):
+    cxx = _compiler()
+    if cxx is None:
+        pytest.skip("no host C++ compiler (g++ or hipcc)")
+    exe = tmp_path / "uniform_decl_test"
+    build = subprocess.run(cxx + FLAGS + SOURCES + ["-o", str(exe)], capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr[-4000:]
+    run = subprocess.run([str(exe)], cwd=tmp_path, capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0, (run.stdout + run.stderr)[-4000:]
+    assert "all checks passed" in run.stdout
