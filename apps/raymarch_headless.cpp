@@ -18,11 +18,15 @@
 //          [--format rgba8|float] [--stats] [--warmup N]
 //          [--post] [--post-sample fxaa|chromatic|texel]
 //          [--tonemap none|aces|reinhard|jodie|uncharted2]
-//          [--uniform name=v[,v...]]...
+//          [--uniform name=v[,v...]]... [--pick X,Y]
 // --uniform sets a uniform the scene declares itself (a scene plugin's
 // `uniform vec4 u_ball = ...;`, rm.h rm_load_scene) once the scene is loaded:
 // one to four numbers for a float / vec2 / vec3 / vec4, one for an int or a
 // bool; repeatable.
+// --pick X,Y prints a JSON line about what is under pixel (X, Y) of the last
+// frame drawn: the pixel's ray from rm::Shader::cameraRays, cast with
+// castRays (rm.h rm_cast_rays): status, t, position, normal and the
+// material's diffuse colour.
 // Frames are drawn into the RGBA8 target the reference renders into
 // (--format float: RGBA32F) and queued without a host synchronization per
 // frame; --stats times each frame's kernel (HIP events, which waits for every
@@ -50,6 +54,7 @@ int main(int argc, char** argv) {
     int mdx = 0, mdy = 0;
     bool time_freeze = false, sharded = false, accumulate = false, stats = false, fmt_float = false;
     int warmup = 0;
+    int pick_x = -1, pick_y = -1;
     bool post = false;
     rm_post_sample post_sample = RM_POST_SAMPLE_FXAA;
     rm_tonemap tonemap = RM_TONEMAP_NONE;
@@ -110,6 +115,12 @@ int main(int argc, char** argv) {
             tonemap = (rm_tonemap)k;
         }
         else if (a == "--mouse") std::sscanf(next().c_str(), "%d,%d", &mdx, &mdy);
+        else if (a == "--pick") {
+            if (std::sscanf(next().c_str(), "%d,%d", &pick_x, &pick_y) != 2 || pick_x < 0 || pick_y < 0) {
+                std::fprintf(stderr, "--pick X,Y\n");
+                return 2;
+            }
+        }
         else if (a == "--uniform") {
             const std::string u = next();
             const size_t eq = u.find('=');
@@ -288,6 +299,33 @@ int main(int argc, char** argv) {
                 frames, warmup, w, h, gpus, scene.c_str(), sharded || !fmt_float ? "rgba8" : "float", frames / wall);
     if (stats) std::printf("\"kernel_ms_per_frame\": %.4f, ", frames ? kernel_ms / frames : 0.0);
     std::printf("\"pos\": [%.4f, %.4f, %.4f]}\n", pos.x, pos.y, pos.z);
+    if (pick_x >= 0) {  // the uniforms are the last frame's
+        if (pick_x >= w || pick_y >= h) {
+            std::fprintf(stderr, "--pick %d,%d outside the %dx%d frame\n", pick_x, pick_y, w, h);
+            return 2;
+        }
+        rm::Vec3 origin{0.0f, 0.0f, 0.0f}, position, normal;
+        std::vector<rm::Vec3> dirs((size_t)w * h);
+        float t = 0.0f, material[16];
+        int32_t status = 0;
+        rm_ray_hits hits;
+        std::memset(&hits, 0, sizeof(hits));
+        hits.t = &t;
+        hits.status = &status;
+        hits.position = &position.x;
+        hits.normal = &normal.x;
+        hits.material = material;
+        if (!shader.cameraRays(w, h, &origin, dirs.data()) ||
+            !shader.castRays(&origin, true, &dirs[(size_t)pick_y * w + pick_x], 1, hits)) {
+            std::fprintf(stderr, "--pick failed: %s\n", shader.lastError().c_str());
+            return 1;
+        }
+        std::printf("{\"pick\": [%d, %d], \"status\": \"%s\", \"t\": %.9g, \"position\": [%.9g, %.9g, %.9g], "
+                    "\"normal\": [%.9g, %.9g, %.9g], \"diffuse\": [%.9g, %.9g, %.9g]}\n",
+                    pick_x, pick_y, status == RM_RAY_HIT ? "hit" : status == RM_RAY_MISS ? "miss" : "exhausted", t,
+                    position.x, position.y, position.z, normal.x, normal.y, normal.z, material[0], material[1],
+                    material[2]);
+    }
     if (!ppm.empty()) {
         std::vector<uint32_t> px;
         if (!sharded ? !outputTexture.copyToHostRGBA8(shader, px) : !shardedTexture.copyToHostRGBA8(px)) return 1;

@@ -168,6 +168,51 @@ rm_status rm_compile_scene(const char *file_name, char *log, size_t log_size);
  * returns when the results are written.  Uniforms (u_time ...) are the ctx's. */
 rm_status rm_scene_eval(rm_ctx *ctx, const float *points, int64_t n, float *dist, float *material);
 
+/* Ray queries: castRayD (common.frag:879-901; castRayDI, :903-925, when
+ * inside != 0) of the loaded scene along n caller-supplied rays, the march the
+ * render kernels run first for every pixel, on its own: picking, camera
+ * collision, placing things on a surface, depth and normal buffers.
+ * origins: n xyz float triples, or one triple for all rays when shared_origin
+ * != 0; directions: n triples, used as given (not normalised: t is in units
+ * of |direction|).  The loop is the reference's over rm_params.max_steps with
+ * ZNEAR 0.02 and ZFAR 50 (max_steps = 0: t = 0, RM_RAY_EXHAUSTED, 0 steps), in
+ * the reference's arithmetic (every scene's exact form, as rm_scene_eval's
+ * distances).  Uniforms (u_time, a plugin's own) are the ctx's, read at the
+ * call.
+ * rm_ray_hits: every pointer may be NULL (not written) except t.  All buffers
+ * of a call, inputs included, are device pointers or all are host pointers; a
+ * mix is RM_ERR_INVALID_ARGUMENT.  Device: asynchronous on the ctx stream
+ * unless `stats` is given; then the call waits and fills kernel_ms, pixels = n,
+ * evals = the sum of `steps`, scene.  Host: staged, returns when the results
+ * are written.  n < 0, n > 2^30, or a NULL origins / directions / out / out->t
+ * with n > 0: RM_ERR_INVALID_ARGUMENT; no scene: RM_ERR_NO_SCENE; n = 0: RM_OK,
+ * nothing launched (all checked before any pointer is used). */
+enum { RM_RAY_MISS = 0, RM_RAY_HIT = 1, RM_RAY_EXHAUSTED = 2 };
+typedef struct rm_ray_hits {
+    float *t;         /* n: castRayD's dist: the depth on a hit, -1 past ZFAR, the last sceneSDF value
+                         when max_steps ran out                                                   */
+    int32_t *status;  /* n: RM_RAY_*                                                             */
+    uint32_t *steps;  /* n: sceneSDF calls of the march                                          */
+    float *position;  /* n x 3: origin + direction * t where t > 0 (the point render() shades,
+                         output_shader.frag:351-355), else 0                                     */
+    float *normal;    /* n x 3: getNormalFast(position) (common.frag:697-708) where t > 0, else 0 */
+    float *material;  /* n x 16: the Material of the SdResult castRayD returns (sceneSDF at the last
+                         point evaluated; the origin without steps), in the order of
+                         rm_scene_eval's; scene O's floor colour in the CPU restatement's
+                         arithmetic (C library sin and pow), within 6e-6 of a frame's           */
+} rm_ray_hits;
+rm_status rm_cast_rays(rm_ctx *ctx, const float *origins, int shared_origin, const float *directions, int64_t n,
+                       int inside, const rm_ray_hits *out, rm_stats *stats);
+
+/* The rays main() builds for a W x H frame (output_shader.frag:388-405,
+ * template.frag:78-88) from u_resolution, u_pos and u_mouse: u_pos into
+ * origin3 (3 floats), one direction per pixel into directions (W*H*3 floats,
+ * row 0 first, pixel centres, no jitter), in the arithmetic of the loaded
+ * scene's render kernel.  Each buffer device (asynchronous on the ctx stream)
+ * or host.  rm_cast_rays of these rays with shared_origin = 1 gives the
+ * frame's depth / normal / material buffers.  W*H <= 2^30. */
+rm_status rm_camera_rays(rm_ctx *ctx, int W, int H, float *origin3, float *directions);
+
 /* Replace sf::Shader::setUniform (include/SFML/Graphics/Shader.hpp:297,306,315)
  * for the names main.cpp sets: u_resolution (2f), u_pos (3f), u_mouse (2f),
  * u_time (1f), u_sample_part (1f), u_seed1/u_seed2 (2f).  The last three are

@@ -107,6 +107,21 @@ public:
         return rm_set_params(ctx_, &p) == RM_OK;
     }
 
+    // Ray queries (rm.h rm_cast_rays, rm_camera_rays; no counterpart in the
+    // reference, whose castRayD is only reachable inside a frame's shading):
+    // the rays main() builds for a w x h frame, and castRayD along any rays.
+    // Buffers are all device or all host pointers, as the C calls take them.
+    bool cameraRays(int w, int h, Vec3* origin, Vec3* directions) {
+        return ctx_ && rm_camera_rays(ctx_, w, h, reinterpret_cast<float*>(origin),
+                                      reinterpret_cast<float*>(directions)) == RM_OK;
+    }
+    bool castRays(const Vec3* origins, bool sharedOrigin, const Vec3* directions, std::int64_t n,
+                  const rm_ray_hits& hits, bool inside = false, rm_stats* stats = nullptr) {
+        return ctx_ && rm_cast_rays(ctx_, reinterpret_cast<const float*>(origins), sharedOrigin ? 1 : 0,
+                                    reinterpret_cast<const float*>(directions), n, inside ? 1 : 0, &hits,
+                                    stats) == RM_OK;
+    }
+
 private:
     bool setArray(const char* name, int components, const float* v, std::size_t length) {
         return ctx_ && length <= 64 && rm_set_uniformfv(ctx_, name, components, v, (int)length) == RM_OK;

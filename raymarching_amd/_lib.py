@@ -32,7 +32,7 @@ EXPORTS = ("rm_create", "rm_destroy", "rm_load_scene", "rm_set_uniform1f", "rm_s
            "rm_render_sharded_runs", "rm_render_sharded_runs_all", "rm_wire_capacity", "rm_wire_workspace_bytes",
            "rm_wire_encode", "rm_wire_decode", "rm_scatter_part_rgba8", "rm_wire_decode_parts",
            "rm_set_uniform4f", "rm_set_uniform1i", "rm_set_uniformfv", "rm_uniform_count", "rm_uniform_info_at",
-           "rm_get_uniformfv", "rm_get_uniform1i")
+           "rm_get_uniformfv", "rm_get_uniform1i", "rm_cast_rays", "rm_camera_rays")
 
 # include/rm.h RM_ABI_VERSION: the struct layouts below
 ABI_VERSION = 3
@@ -71,6 +71,15 @@ class RmUniformInfo(ctypes.Structure):
 
 
 UNIFORM_TYPES = {0: "float", 1: "int", 2: "bool"}  # include/rm.h rm_uniform_type
+
+
+class RmRayHits(ctypes.Structure):
+    """include/rm.h rm_ray_hits: the outputs of rm_cast_rays (NULL: not written; t is required)."""
+    _fields_ = [("t", ctypes.c_void_p), ("status", ctypes.c_void_p), ("steps", ctypes.c_void_p),
+                ("position", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("material", ctypes.c_void_p)]
+
+
+RAY_STATUS = {0: "miss", 1: "hit", 2: "exhausted"}  # include/rm.h RM_RAY_*
 
 
 class RmCommId(ctypes.Structure):
@@ -150,6 +159,8 @@ def lib() -> ctypes.CDLL:
                                        c.POINTER(RmStats)], c.c_int),
         "rm_compile_scene": ([cp, vp, c.c_size_t], c.c_int),
         "rm_scene_eval": ([vp, vp, c.c_int64, vp, vp], c.c_int),
+        "rm_cast_rays": ([vp, vp, c.c_int, vp, c.c_int64, c.c_int, c.POINTER(RmRayHits), c.POINTER(RmStats)], c.c_int),
+        "rm_camera_rays": ([vp, c.c_int, c.c_int, vp, vp], c.c_int),
         "rm_sharded_layout": ([c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.POINTER(RmShardLayout)], c.c_int),
         "rm_comm_get_id": ([c.POINTER(RmCommId)], c.c_int),
         "rm_comm_init_rank": ([c.POINTER(vp), vp, c.c_int, c.POINTER(RmCommId), c.c_int], c.c_int),

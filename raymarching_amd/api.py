@@ -491,6 +491,63 @@ class Renderer:
                                   self._ptr(mat) if material else None), self._ctx)
         return (dist, mat) if material else dist
 
+    def cast_rays(self, origins, directions, inside: bool = False, normal: bool = True, material: bool = False,
+                  stats: bool = False) -> dict:
+        """rm_cast_rays: castRayD (castRayDI with inside=True) of the loaded
+        scene along rays directions [n, 3] (used as given, not normalised) from
+        origins [n, 3], or [3] for one origin shared by all rays.  numpy
+        arrays: staged, numpy results.  torch tensors on this renderer's
+        device: the results are device tensors and the call is asynchronous on
+        the renderer's stream (unless stats=True).  Returns dict(t [n] f32,
+        status [n] i32 (RM_RAY_*), steps [n] i32, position [n, 3][, normal
+        [n, 3]][, material [n, 16]][, stats])."""
+        import numpy as np
+        on_device = hasattr(directions, "data_ptr") and directions.is_cuda
+        if on_device:
+            torch = _torch()
+            dev = directions.device
+            d = directions.to(torch.float32).reshape(-1, 3).contiguous()
+            o = torch.as_tensor(origins, dtype=torch.float32, device=dev).contiguous()
+
+            def empty(shape, dtype=torch.float32):
+                return torch.empty(shape, dtype=dtype, device=dev)
+            i32 = torch.int32
+        else:
+            d = np.ascontiguousarray(np.asarray(directions), np.float32).reshape(-1, 3)
+            o = np.ascontiguousarray(np.asarray(origins), np.float32)
+
+            def empty(shape, dtype=np.float32):
+                return np.empty(shape, dtype)
+            i32 = np.int32
+        n = len(d)
+        shared = o.ndim == 1
+        if tuple(o.shape) != ((3,) if shared else (n, 3)):
+            raise ValueError(f"cast_rays: origins {tuple(o.shape)} for {n} directions; expected [3] or [{n}, 3]")
+        out = dict(t=empty(n), status=empty(n, i32), steps=empty(n, i32), position=empty((n, 3)))
+        if normal:
+            out["normal"] = empty((n, 3))
+        if material:
+            out["material"] = empty((n, 16))
+        hits = _lib.RmRayHits(*(self._ptr(out[k]) if k in out and n else None
+                                for k in ("t", "status", "steps", "position", "normal", "material")))
+        s = RmStats()
+        check(lib().rm_cast_rays(self._ctx, self._ptr(o), int(shared), self._ptr(d), n, int(bool(inside)),
+                                 ctypes.byref(hits), ctypes.byref(s) if stats else None), self._ctx)
+        if stats:
+            out["stats"] = s.as_dict()
+        return out
+
+    def camera_rays(self, W: int, H: int):
+        """rm_camera_rays: (origin [3], directions [H, W, 3]) on the device, the
+        rays main() builds for the W x H frame; cast_rays(origin, directions.
+        reshape(-1, 3)) gives the frame's depth / normal / material buffers."""
+        torch = _torch()
+        dev = f"cuda:{self.device}"
+        origin = torch.empty(3, dtype=torch.float32, device=dev)
+        directions = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+        check(lib().rm_camera_rays(self._ctx, int(W), int(H), self._ptr(origin), self._ptr(directions)), self._ctx)
+        return origin, directions
+
     def render_rgba8(self, W, H, out=None, stats=False):
         torch = _torch()
         if out is None:

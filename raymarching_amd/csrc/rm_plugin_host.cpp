@@ -291,6 +291,7 @@ hipError_t load(const Code& code, int uniform_slots, Module& m) {
         n.render = n.render_count = nullptr;
     }
     e = hipModuleGetFunction(&n.eval, n.mod, "rm_plugin_eval");
+    if (e == hipSuccess) e = hipModuleGetFunction(&n.cast, n.mod, "rm_plugin_cast");
     if (e != hipSuccess) {
         (void)hipModuleUnload(n.mod);
         return e;
@@ -336,6 +337,20 @@ hipError_t launch_eval(const Module& m, const rm::FrameConst& F, const uint32_t*
     void* with_block[] = {&f, const_cast<uint32_t*>(uniforms), &p, &nn, &d, &mm};
     void* args[] = {&f, &p, &nn, &d, &mm};
     return hipModuleLaunchKernel(m.eval, (unsigned)((n + 255) / 256), 1, 1, 256, 1, 1, 0, s,
+                                 m.uniform_slots > 0 ? with_block : args, nullptr);
+}
+
+hipError_t launch_cast(const Module& m, const rm::FrameConst& F, const uint32_t* uniforms, const rm::RayQuery& Q,
+                       int inside, int block, hipStream_t s) {
+    if (Q.n <= 0) return hipSuccess;
+    if (!m.cast) return hipErrorInvalidDeviceFunction;
+    rm::FrameConst f = F;
+    rm::RayQuery q = Q;
+    int in = inside;
+    // (the uniform block is read now, as launch_eval's)
+    void* with_block[] = {&f, const_cast<uint32_t*>(uniforms), &q, &in};
+    void* args[] = {&f, &q, &in};
+    return hipModuleLaunchKernel(m.cast, (unsigned)((Q.n + block - 1) / block), 1, 1, (unsigned)block, 1, 1, 0, s,
                                  m.uniform_slots > 0 ? with_block : args, nullptr);
 }
 

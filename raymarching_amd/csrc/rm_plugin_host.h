@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "rm_device.h"
+#include "rm_rays.h"
 #include "rm_uniform_decl.h"
 
 namespace rmplugin {
@@ -37,6 +38,7 @@ struct Module {
     hipFunction_t render = nullptr;        // timed render kernel; null for an RM_PLUGIN_EVAL_ONLY scene
     hipFunction_t render_count = nullptr;  // instrumented render kernel (ray-step counts, step maps)
     hipFunction_t eval = nullptr;
+    hipFunction_t cast = nullptr;          // rm_cast_rays' march (RM_PLUGIN_EVAL_ONLY scenes have it too)
     Code code;
     int uniform_slots = 0;  // > 0: the kernels take the uniform block as their second argument (rm_plugin.h)
 };
@@ -49,5 +51,8 @@ hipError_t launch_render(const Module& m, const rm::FrameConst& F, const uint32_
                          unsigned long long* evals, hipStream_t s);
 hipError_t launch_eval(const Module& m, const rm::FrameConst& F, const uint32_t* uniforms, const float* pts,
                        long long n, float* dist, float* mat, hipStream_t s);
+// `block`: threads per workgroup (rm::cast_block_size)
+hipError_t launch_cast(const Module& m, const rm::FrameConst& F, const uint32_t* uniforms, const rm::RayQuery& Q,
+                       int inside, int block, hipStream_t s);
 
 }  // namespace rmplugin

@@ -6,6 +6,7 @@
 // (rm_plugin.h UniformBlock: read from the kernel-argument segment, so the
 // parameter itself is never named), loaded once at the top of each kernel.
 #pragma once
+#include "rm_rays.h"
 
 #ifdef RM_UNIFORM_SLOTS
 #define RM_UNIFORM_PARAM rm::glsl::UniformBlock,
@@ -84,4 +85,11 @@ extern "C" __global__ __launch_bounds__(256) void rm_plugin_eval(rm::FrameConst 
                                                                  long long n, float* dist, float* mat) {
     RM_UNIFORM_PRELOAD();
     rm::scene_eval_one<rm::SCENE_PLUGIN>(F, pts, n, dist, mat);
+}
+
+// castRayD / castRayDI over caller-supplied rays (rm_cast_rays, rm_rays.h)
+extern "C" __global__ __launch_bounds__(256) void rm_plugin_cast(rm::FrameConst F, RM_UNIFORM_PARAM rm::RayQuery Q,
+                                                                 int inside) {
+    RM_UNIFORM_PRELOAD();
+    rm::cast_rays_one<rm::SCENE_PLUGIN>(F, Q, inside);
 }

@@ -1,0 +1,169 @@
+// rm_rays_host.cpp -- rm_cast_rays and rm_camera_rays (include/rm.h): their
+// argument checks, the staging of host buffers and the launches (kernels:
+// rm_rays.h, rm_rays.hip; a scene plugin's: rm_plugin_kernels.h).
+#include <cstring>
+
+#include "rm_ctx.h"
+#include "rm_rays.h"
+#include "rm_trace.h"
+
+using rm::FrameConst;
+using rm::RowPart;
+using namespace rmhost;
+
+static_assert((int)RM_RAY_MISS == (int)rm::RAY_MISS && (int)RM_RAY_HIT == (int)rm::RAY_HIT &&
+                  (int)RM_RAY_EXHAUSTED == (int)rm::RAY_EXHAUSTED,
+              "rm.h RM_RAY_* and rm_rays.h RAY_*");
+
+namespace {
+
+constexpr int64_t kMaxRays = (int64_t)1 << 30;
+
+// the launch on the context's stream, with the stats of an instrumented one
+rm_status cast_dev(rm_ctx *ctx, rm::RayQuery Q, int inside, rm_stats *stats) {
+    rm::TraceRange range("rm_cast_rays");
+    const FrameConst F = frame_const(ctx, 1, 1, RowPart{1, 0, 1}, 1);
+    if (stats) {
+        Q.evals = ctx->d_evals;
+        RM_HIP(hipMemsetAsync(ctx->d_evals, 0, 3 * sizeof(unsigned long long), ctx->stream));
+        RM_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+    }
+    const hipError_t e =
+        ctx->scene == rm::SCENE_PLUGIN
+            ? rmplugin::launch_cast(ctx->plugin, F, ctx->uniform_values, Q, inside, rm::cast_block_size(), ctx->stream)
+            : rm::launch_cast_rays(ctx->scene, F, Q, inside, ctx->stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "cast kernel launch");
+    mark_done(ctx);
+    if (stats) {
+        RM_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+        RM_HIP(hipEventSynchronize(ctx->ev1));
+        float ms = 0.0f;
+        RM_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+        unsigned long long ev = 0;
+        RM_HIP(hipMemcpy(&ev, ctx->d_evals, sizeof(ev), hipMemcpyDeviceToHost));
+        std::memset(stats, 0, sizeof(*stats));
+        stats->evals = ev;
+        stats->pixels = (uint64_t)Q.n;
+        stats->kernel_ms = ms;
+        stats->scene = ctx->scene;
+    }
+    return RM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+rm_status rm_cast_rays(rm_ctx *ctx, const float *origins, int shared_origin, const float *directions, int64_t n,
+                       int inside, const rm_ray_hits *out, rm_stats *stats) {
+    if (!ctx) return RM_ERR_INVALID_ARGUMENT;
+    if (n < 0 || n > kMaxRays || (n > 0 && (!origins || !directions || !out || !out->t)))
+        return fail(ctx, RM_ERR_INVALID_ARGUMENT, "rm_cast_rays: bad arguments");
+    if (ctx->scene < 0) return fail(ctx, RM_ERR_NO_SCENE, "no scene loaded (rm_load_scene)");
+    if (n == 0) return RM_OK;
+    RM_HIP(hipSetDevice(ctx->device));
+    // the buffers in use, their sizes in floats per ray (origins: per launch when shared)
+    struct Buf {
+        const void *p;
+        size_t bytes;
+        bool input;
+    };
+    const size_t f = sizeof(float), N = (size_t)n;
+    const Buf bufs[8] = {{origins, (shared_origin ? 1 : N) * 3 * f, true}, {directions, N * 3 * f, true},
+                         {out->t, N * f, false},            {out->status, N * f, false},
+                         {out->steps, N * f, false},        {out->position, N * 3 * f, false},
+                         {out->normal, N * 3 * f, false},   {out->material, N * 16 * f, false}};
+    int ndev = 0, nused = 0;
+    size_t total = 0;
+    for (const Buf &b : bufs) {
+        if (!b.p) continue;
+        nused++;
+        ndev += is_device_ptr(b.p) ? 1 : 0;
+        total += (b.bytes + 255) & ~(size_t)255;
+    }
+    if (ndev != 0 && ndev != nused)
+        return fail(ctx, RM_ERR_INVALID_ARGUMENT, "rm_cast_rays: host and device pointers mixed");
+    rm::RayQuery Q;
+    std::memset(&Q, 0, sizeof(Q));
+    Q.n = n;
+    Q.shared_origin = shared_origin ? 1 : 0;
+    if (ndev) {
+        Q.origins = origins;
+        Q.directions = directions;
+        Q.t = out->t;
+        Q.status = out->status;
+        Q.steps = out->steps;
+        Q.position = out->position;
+        Q.normal = out->normal;
+        Q.material = out->material;
+        return cast_dev(ctx, Q, inside, stats);
+    }
+    // host buffers: staged, and the call returns when the results are written
+    char *tmp = nullptr;
+    RM_HIP(hipMalloc(&tmp, total));
+    void *dev[8] = {};
+    size_t off = 0;
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 8; k++) {
+        if (!bufs[k].p) continue;
+        dev[k] = tmp + off;
+        off += (bufs[k].bytes + 255) & ~(size_t)255;
+        if (bufs[k].input && e == hipSuccess)
+            e = hipMemcpyAsync(dev[k], bufs[k].p, bufs[k].bytes, hipMemcpyHostToDevice, ctx->stream);
+    }
+    Q.origins = static_cast<const float *>(dev[0]);
+    Q.directions = static_cast<const float *>(dev[1]);
+    Q.t = static_cast<float *>(dev[2]);
+    Q.status = static_cast<int *>(dev[3]);
+    Q.steps = static_cast<uint32_t *>(dev[4]);
+    Q.position = static_cast<float *>(dev[5]);
+    Q.normal = static_cast<float *>(dev[6]);
+    Q.material = static_cast<float *>(dev[7]);
+    rm_status st = e == hipSuccess ? cast_dev(ctx, Q, inside, stats) : hip_fail(ctx, e, "rm_cast_rays: staging");
+    for (int k = 2; k < 8 && st == RM_OK; k++) {
+        if (!bufs[k].p) continue;
+        e = hipMemcpyAsync(const_cast<void *>(bufs[k].p), dev[k], bufs[k].bytes, hipMemcpyDeviceToHost, ctx->stream);
+        if (e != hipSuccess) st = hip_fail(ctx, e, "rm_cast_rays: staging");
+    }
+    e = hipStreamSynchronize(ctx->stream);  // (also after a failure: tmp may be in use)
+    if (st == RM_OK && e != hipSuccess) st = hip_fail(ctx, e, "rm_cast_rays");
+    (void)hipFree(tmp);
+    return st;
+}
+
+rm_status rm_camera_rays(rm_ctx *ctx, int W, int H, float *origin3, float *directions) {
+    if (!ctx) return RM_ERR_INVALID_ARGUMENT;
+    if (W <= 0 || H <= 0 || (int64_t)W * H > kMaxRays || !origin3 || !directions)
+        return fail(ctx, RM_ERR_INVALID_ARGUMENT, "rm_camera_rays: bad arguments");
+    if (ctx->scene < 0) return fail(ctx, RM_ERR_NO_SCENE, "no scene loaded (rm_load_scene)");
+    RM_HIP(hipSetDevice(ctx->device));
+    rm::TraceRange range("rm_camera_rays");
+    const bool dev_o = is_device_ptr(origin3), dev_d = is_device_ptr(directions);
+    const size_t bytes = (size_t)W * H * 3 * sizeof(float);
+    const FrameConst F = frame_const(ctx, W, H, RowPart{1, 0, 1}, H);
+    // the form of the loaded scene's render kernel (a plugin's: output_shader.frag's pass)
+    const bool fast = ctx->scene == rm::SCENE_S0   ? rm::ScenePolicy<rm::SCENE_S0>::kHwMath
+                      : ctx->scene == rm::SCENE_T  ? rm::ScenePolicy<rm::SCENE_T>::kHwMath
+                      : ctx->scene == rm::SCENE_O  ? rm::ScenePolicy<rm::SCENE_O>::kHwMath
+                      : ctx->scene == rm::SCENE_OG ? rm::ScenePolicy<rm::SCENE_OG>::kHwMath
+                                                   : rm::ScenePolicy<rm::SCENE_PLUGIN>::kHwMath;
+    float *tmp = nullptr;
+    if (!dev_d) RM_HIP(hipMalloc(&tmp, bytes));
+    if (!dev_o) {
+        origin3[0] = F.pos_x;
+        origin3[1] = F.pos_y;
+        origin3[2] = F.pos_z;
+    }
+    hipError_t e = rm::launch_camera_rays(fast, F, dev_o ? origin3 : nullptr, dev_d ? directions : tmp, ctx->stream);
+    if (e == hipSuccess) mark_done(ctx);
+    if (e == hipSuccess && !dev_d) e = hipMemcpyAsync(directions, tmp, bytes, hipMemcpyDeviceToHost, ctx->stream);
+    if (!dev_d) {
+        const hipError_t es = hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = es;
+        (void)hipFree(tmp);
+    }
+    if (e != hipSuccess) return hip_fail(ctx, e, "rm_camera_rays");
+    return RM_OK;
+}
+
+}  // extern "C"
