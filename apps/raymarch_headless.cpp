@@ -18,7 +18,13 @@
 //          [--format rgba8|float] [--stats] [--warmup N]
 //          [--post] [--post-sample fxaa|chromatic|texel]
 //          [--tonemap none|aces|reinhard|jodie|uncharted2]
-//          [--uniform name=v[,v...]]... [--pick X,Y]
+//          [--uniform name=v[,v...]]... [--pick X,Y] [--aa K[:threshold]]
+// --aa K[:threshold] draws each frame with adaptive supersampling
+// (rm::RenderTexture::drawAA -> rm_render_aa_rgba8): K = 2, 4 or 8 samples at
+// the pixels whose 3x3 neighbourhood spreads a colour channel by at least
+// threshold (0..255, default 32; 0: every pixel).  One GPU, the RGBA8 target,
+// built-in scenes; --stats then counts the base frame's, the detect and the
+// refine kernel.
 // --uniform sets a uniform the scene declares itself (a scene plugin's
 // `uniform vec4 u_ball = ...;`, rm.h rm_load_scene) once the scene is loaded:
 // one to four numbers for a float / vec2 / vec3 / vec4, one for an int or a
@@ -55,6 +61,7 @@ int main(int argc, char** argv) {
     bool time_freeze = false, sharded = false, accumulate = false, stats = false, fmt_float = false;
     int warmup = 0;
     int pick_x = -1, pick_y = -1;
+    int aa_samples = 0, aa_threshold = 32;  // --aa (0: off)
     bool post = false;
     rm_post_sample post_sample = RM_POST_SAMPLE_FXAA;
     rm_tonemap tonemap = RM_TONEMAP_NONE;
@@ -121,6 +128,16 @@ int main(int argc, char** argv) {
                 return 2;
             }
         }
+        else if (a == "--aa") {
+            const std::string v = next();
+            char tail = 0;
+            const int got = std::sscanf(v.c_str(), "%d:%d%c", &aa_samples, &aa_threshold, &tail);
+            if ((got != 1 && got != 2) || (got == 1 && v.find(':') != std::string::npos) ||
+                (aa_samples != 2 && aa_samples != 4 && aa_samples != 8) || aa_threshold < 0 || aa_threshold > 255) {
+                std::fprintf(stderr, "--aa K[:threshold]  (K = 2, 4 or 8; threshold 0..255)\n");
+                return 2;
+            }
+        }
         else if (a == "--uniform") {
             const std::string u = next();
             const size_t eq = u.find('=');
@@ -163,6 +180,10 @@ int main(int argc, char** argv) {
     }
     if (post && (gpus > 1 || sharded || accumulate || fmt_float)) {
         std::fprintf(stderr, "--post runs on the one-GPU RGBA8 target, without --accumulate\n");
+        return 2;
+    }
+    if (aa_samples && (gpus > 1 || sharded || accumulate || fmt_float)) {
+        std::fprintf(stderr, "--aa draws on the one-GPU RGBA8 target, without --accumulate\n");
         return 2;
     }
     // one shader (librm context) per GPU; the first is the reference's `shader`
@@ -270,11 +291,14 @@ int main(int argc, char** argv) {
         setAll("u_seed2", seed2);
         std::vector<rm_stats> st(gpus);
         rm_stats* stp = stats ? st.data() : nullptr;
+        rm_aa_stats aa_st;
         // --accumulate: the pass reads u_sample/u_sample_part/u_seed1 (progressive
         // supersampling while the camera is still; one GPU)
         const bool drawn = sharded      ? shardedTexture.draw(stp)
                            : accumulate ? outputTexture.drawAccumulate(shader, stp)
+                           : aa_samples ? outputTexture.drawAA(shader, aa_samples, aa_threshold, stats ? &aa_st : nullptr)
                                         : outputTexture.draw(shader, stp);
+        if (drawn && aa_samples && stats) st[0].kernel_ms = aa_st.base_ms + aa_st.detect_ms + aa_st.refine_ms;
         if (!drawn) {
             std::fprintf(stderr, "draw failed: %s\n", shader.lastError().c_str());
             return 1;

@@ -364,6 +364,60 @@ rm_status rm_render_rgba8(rm_ctx *ctx, int W, int H, uint32_t *out, rm_stats *st
 rm_status rm_render_accumulate(rm_ctx *ctx, int W, int H, float *accum, rm_stats *stats);
 rm_status rm_render_accumulate_rgba8(rm_ctx *ctx, int W, int H, uint32_t *accum, rm_stats *stats);
 
+/* Adaptive supersampling: one antialiased RGBA8 frame from one call (no
+ * counterpart in the reference, whose main() is labelled "NO AA").  The edge
+ * pixels of a frame are found on its RGBA8 words and only those are rendered
+ * again, `samples` times each, in one launch sequence on the ctx stream with
+ * no host round trip.
+ *   Edge rule (integer, exact): pixel (x, y) is an edge pixel iff for some
+ * channel of R, G, B the largest byte over the pixel's 3x3 neighbourhood minus
+ * the smallest is >= threshold (0..255); neighbour coordinates are clamped to
+ * the frame, alpha is ignored.  Threshold 0: every pixel.
+ *   Samples: K = 2, 4 or 8 offsets from the pixel centre, in pixels (K = 4 a
+ * rotated grid; rm_aa_offsets lists them).  Every offset o and o + 0.5 is exact
+ * in f32, so u_seed1 = o + 0.5 makes rm_render_accumulate render that sample.
+ *   A refined pixel is the scene's RGBA8 pack of the mean of its K samples,
+ * each the pass's final colour with the fragment moved by the offset exactly
+ * as rm_render_accumulate moves it, summed as a pairwise tree in sample order
+ * ((s0 + s1) + (s2 + s3)) + ((s4 + s5) + (s6 + s7)) and multiplied by 1 / K in
+ * f32: byte for byte what blending rm_render_accumulate's K jittered float
+ * frames on the host gives.  Every other pixel keeps its bytes.
+ * rm_aa_offsets: the 2 * samples floats x0, y0, x1, y1, ... (host only).
+ * rm_aa_edge_mask: the edge rule on a host frame into mask (W*H bytes, 1 = edge
+ * pixel); host pointers, no GPU.
+ * rm_refine_rgba8: replaces the edge pixels of `frame`, any RGBA8 frame of the
+ * context's current uniforms (normally rm_render_rgba8's), by their K-sample
+ * colour, in place; mask (W*H bytes, 1 = refined) may be NULL.
+ * rm_render_aa_rgba8: rm_render_rgba8 into `out`, then rm_refine_rgba8 of it.
+ * Both: frame and mask are both device pointers (asynchronous on the ctx
+ * stream unless `stats` is given; then the call waits and fills it) or both
+ * host pointers (staged; returns when the results are written).  W, H <= 0,
+ * W*H >= 2^30, a NULL params or frame, samples not 2, 4 or 8, a threshold
+ * outside 0..255 or mixed pointers: RM_ERR_INVALID_ARGUMENT; no scene:
+ * RM_ERR_NO_SCENE; a scene plugin: RM_ERR_SCENE ("adaptive supersampling:
+ * built-in scenes only"), the frame untouched -- all checked before any
+ * pointer is used.  The queue of edge pixels is a scratch buffer of the
+ * context (a word per pixel) with the life and stream rule of rm_bloom's.
+ * Out of scope: scene plugins, float targets, banded / sharded / wire renders
+ * and count_evals of the refine (rm_params.count_evals counts the base frame
+ * only). */
+typedef struct rm_aa_params {
+    int32_t samples;   /* K: 2, 4 or 8 */
+    int32_t threshold; /* 0..255       */
+} rm_aa_params;
+typedef struct rm_aa_stats {
+    int64_t refined;  /* pixels refined (the mask's ones)                                 */
+    float base_ms;    /* rm_render_aa_rgba8: the base frame's kernel (rm_stats.kernel_ms) */
+    float detect_ms;  /* the detect kernel                                                */
+    float refine_ms;  /* the refine kernel                                                */
+} rm_aa_stats;
+rm_status rm_aa_offsets(int samples, float *xy);
+rm_status rm_aa_edge_mask(int W, int H, int threshold, const uint32_t *frame, uint8_t *mask);
+rm_status rm_refine_rgba8(rm_ctx *ctx, int W, int H, const rm_aa_params *params, uint32_t *frame, uint8_t *mask,
+                          rm_aa_stats *stats);
+rm_status rm_render_aa_rgba8(rm_ctx *ctx, int W, int H, const rm_aa_params *params, uint32_t *out, uint8_t *mask,
+                             rm_aa_stats *stats);
+
 /* rm_render_band / rm_render_rows into RGBA8 rows (W uint32 per row). */
 rm_status rm_render_band_rgba8(rm_ctx *ctx, int W, int H, int band, int nshards, int shard, uint32_t *out,
                                rm_stats *stats);

@@ -233,6 +233,16 @@ public:
                               : rm_render_accumulate(shader.ctx(), w_, h_, static_cast<float*>(tex_), stats)) ==
                RM_OK;
     }
+    // draw() with adaptive supersampling (rm_render_aa_rgba8; the reference's
+    // main() is "NO AA"): the frame's edge pixels -- a channel's spread over the
+    // 3x3 neighbourhood >= threshold, 0..255 -- are rendered again with
+    // `samples` (2, 4 or 8) sub-pixel samples and averaged.  RGBA8 targets and
+    // built-in scenes only; the default threshold is a convenience, not tuned.
+    bool drawAA(Shader& shader, int samples = 4, int threshold = 32, rm_aa_stats* stats = nullptr) {
+        if (!tex_ || fmt_ != RGBA8) return false;
+        const rm_aa_params p{samples, threshold};
+        return rm_render_aa_rgba8(shader.ctx(), w_, h_, &p, static_cast<uint32_t*>(tex_), nullptr, stats) == RM_OK;
+    }
     // RenderTarget::draw(sprite, &post_shader) (main.cpp:210): post.frag over the
     // shader's u_main_tex into this RGBA8 target (rm_post_frag)
     bool draw(PostShader& post) {

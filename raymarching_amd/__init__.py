@@ -8,8 +8,8 @@ ShaderLoader / sf::Shader / RenderTexture surface plus the row-sharded
 multi-GPU frame (``frame.py``).
 """
 from ._lib import EXPORTS, LIB_PATH, POST_SAMPLES, TONEMAPS, RmError, lib  # noqa: F401
-from .api import (Comm, Renderer, RenderTexture, Shader, ShaderLoader, comm_get_id, compile_scene,  # noqa: F401
-                  cycle_rows, shard_rows, sharded_layout, wire_capacity, render_code_hash, wire_workspace_bytes)
+from .api import (Comm, Renderer, RenderTexture, Shader, ShaderLoader, aa_edge_mask, aa_offsets,  # noqa: F401
+                  comm_get_id, compile_scene, cycle_rows, shard_rows, sharded_layout, wire_capacity, render_code_hash, wire_workspace_bytes)
 from .poses import POSES, S0_POSE  # noqa: F401
 
 # ray-step (sceneSDF) algorithmic FLOP per scene: SURVEY.md 8(d), DESIGN.md

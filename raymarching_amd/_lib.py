@@ -32,7 +32,8 @@ EXPORTS = ("rm_create", "rm_destroy", "rm_load_scene", "rm_set_uniform1f", "rm_s
            "rm_render_sharded_runs", "rm_render_sharded_runs_all", "rm_wire_capacity", "rm_wire_workspace_bytes",
            "rm_wire_encode", "rm_wire_decode", "rm_scatter_part_rgba8", "rm_wire_decode_parts",
            "rm_set_uniform4f", "rm_set_uniform1i", "rm_set_uniformfv", "rm_uniform_count", "rm_uniform_info_at",
-           "rm_get_uniformfv", "rm_get_uniform1i", "rm_cast_rays", "rm_camera_rays")
+           "rm_get_uniformfv", "rm_get_uniform1i", "rm_cast_rays", "rm_camera_rays",
+           "rm_aa_offsets", "rm_aa_edge_mask", "rm_refine_rgba8", "rm_render_aa_rgba8")
 
 # include/rm.h RM_ABI_VERSION: the struct layouts below
 ABI_VERSION = 3
@@ -77,6 +78,21 @@ class RmRayHits(ctypes.Structure):
     """include/rm.h rm_ray_hits: the outputs of rm_cast_rays (NULL: not written; t is required)."""
     _fields_ = [("t", ctypes.c_void_p), ("status", ctypes.c_void_p), ("steps", ctypes.c_void_p),
                 ("position", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("material", ctypes.c_void_p)]
+
+
+class RmAaParams(ctypes.Structure):
+    """include/rm.h rm_aa_params."""
+    _fields_ = [("samples", ctypes.c_int32), ("threshold", ctypes.c_int32)]
+
+
+class RmAaStats(ctypes.Structure):
+    """include/rm.h rm_aa_stats."""
+    _fields_ = [("refined", ctypes.c_int64), ("base_ms", ctypes.c_float), ("detect_ms", ctypes.c_float),
+                ("refine_ms", ctypes.c_float)]
+
+    def as_dict(self):
+        return dict(refined=int(self.refined), base_ms=float(self.base_ms), detect_ms=float(self.detect_ms),
+                    refine_ms=float(self.refine_ms))
 
 
 RAY_STATUS = {0: "miss", 1: "hit", 2: "exhausted"}  # include/rm.h RM_RAY_*
@@ -161,6 +177,10 @@ def lib() -> ctypes.CDLL:
         "rm_scene_eval": ([vp, vp, c.c_int64, vp, vp], c.c_int),
         "rm_cast_rays": ([vp, vp, c.c_int, vp, c.c_int64, c.c_int, c.POINTER(RmRayHits), c.POINTER(RmStats)], c.c_int),
         "rm_camera_rays": ([vp, c.c_int, c.c_int, vp, vp], c.c_int),
+        "rm_aa_offsets": ([c.c_int, vp], c.c_int),
+        "rm_aa_edge_mask": ([c.c_int, c.c_int, c.c_int, vp, vp], c.c_int),
+        "rm_refine_rgba8": ([vp, c.c_int, c.c_int, c.POINTER(RmAaParams), vp, vp, c.POINTER(RmAaStats)], c.c_int),
+        "rm_render_aa_rgba8": ([vp, c.c_int, c.c_int, c.POINTER(RmAaParams), vp, vp, c.POINTER(RmAaStats)], c.c_int),
         "rm_sharded_layout": ([c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.POINTER(RmShardLayout)], c.c_int),
         "rm_comm_get_id": ([c.POINTER(RmCommId)], c.c_int),
         "rm_comm_init_rank": ([c.POINTER(vp), vp, c.c_int, c.POINTER(RmCommId), c.c_int], c.c_int),

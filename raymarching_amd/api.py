@@ -558,6 +558,70 @@ class Renderer:
               self._ctx)
         return (out, s.as_dict()) if stats else out
 
+    # --- adaptive supersampling (rm_render_aa_rgba8, rm_refine_rgba8) -----
+    def _aa(self, fn, W, H, samples, threshold, frame8, mask, stats):
+        """frame8: [H, W] RGBA8 words, a device tensor or a numpy array (staged);
+        the mask lives where the frame does.  -> frame8[, mask][, stats]."""
+        import numpy as np
+        on_device = hasattr(frame8, "data_ptr")
+        _check_out(frame8, H * W)
+        m = None
+        if mask:
+            m = (_torch().empty((H, W), dtype=_torch().uint8, device=frame8.device) if on_device
+                 else np.empty((H, W), np.uint8))
+        p = _lib.RmAaParams(int(samples), int(threshold))
+        s = _lib.RmAaStats()
+        check(fn(self._ctx, int(W), int(H), ctypes.byref(p), self._ptr(frame8), self._ptr(m) if mask else None,
+                 ctypes.byref(s) if stats else None), self._ctx)
+        res = (frame8,) + ((m,) if mask else ()) + ((s.as_dict(),) if stats else ())
+        return res if len(res) > 1 else frame8
+
+    def render_aa(self, W, H, samples=4, threshold=32, out=None, mask=False, stats=False):
+        """One antialiased RGBA8 frame (rm_render_aa_rgba8): render_rgba8's frame
+        with its edge pixels -- a colour channel's spread over the 3x3
+        neighbourhood >= threshold, 0..255 -- replaced by the mean of `samples`
+        (2, 4 or 8) sub-pixel samples, byte for byte what blending
+        render_accumulate's jittered frames gives there.  The default
+        threshold 32 is a convenience, not a tuned value; 0 supersamples every
+        pixel.  out: [H, W] int32 device tensor (allocated if None) or a numpy
+        array.  Returns out, then with mask=True the uint8 [H, W] mask of the
+        refined pixels, then with stats=True dict(refined, base_ms, detect_ms,
+        refine_ms) (which waits for the frame).  Built-in scenes only."""
+        if out is None:
+            out = _torch().empty((H, W), dtype=_torch().int32, device=f"cuda:{self.device}")
+        return self._aa(lib().rm_render_aa_rgba8, W, H, samples, threshold, out, mask, stats)
+
+    def refine(self, frame8, samples=4, threshold=32, mask=False, stats=False):
+        """rm_refine_rgba8: the supersampling step of render_aa on any [H, W]
+        RGBA8 frame of the current uniforms (normally render_rgba8's), in
+        place; returns as render_aa does."""
+        H, W = frame8.shape
+        return self._aa(lib().rm_refine_rgba8, W, H, samples, threshold, frame8, mask, stats)
+
+
+def aa_offsets(samples: int):
+    """rm_aa_offsets: the [samples, 2] float32 sub-pixel offsets (x, y), in
+    pixels from the pixel centre, of render_aa's samples (samples = 2, 4, 8)."""
+    import numpy as np
+    xy = np.zeros((max(int(samples), 0), 2), np.float32)
+    buf = xy if xy.size else np.zeros((1, 2), np.float32)
+    check(lib().rm_aa_offsets(int(samples), ctypes.c_void_p(buf.ctypes.data)))
+    return xy
+
+
+def aa_edge_mask(frame, threshold: int):
+    """rm_aa_edge_mask: render_aa's edge rule on a host [H, W] RGBA8 frame
+    (numpy, 32-bit words) -> uint8 [H, W], 1 = edge pixel.  No GPU."""
+    import numpy as np
+    f = np.ascontiguousarray(frame)
+    if f.ndim != 2 or f.itemsize != 4:
+        raise ValueError("aa_edge_mask: an [H, W] array of RGBA8 words")
+    H, W = f.shape
+    mask = np.empty((H, W), np.uint8)
+    check(lib().rm_aa_edge_mask(int(W), int(H), int(threshold), ctypes.c_void_p(f.ctypes.data),
+                                ctypes.c_void_p(mask.ctypes.data)))
+    return mask
+
 
 def sharded_layout(W: int, H: int, band: int, nranks: int, rank: int) -> dict:
     """rm_sharded_layout: the row/byte layout of rm_render_sharded (no GPU)."""

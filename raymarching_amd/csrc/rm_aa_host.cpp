@@ -1,0 +1,132 @@
+// rm_aa_host.cpp -- rm_refine_rgba8 and rm_render_aa_rgba8 (include/rm.h):
+// their argument checks, the context's queue, the staging of host buffers and
+// the launch sequence (kernels: rm_aa.h, rm_aa_t.hip, rm_aa_o.hip).
+#include <cstring>
+
+#include "rm_aa.h"
+#include "rm_ctx.h"
+#include "rm_trace.h"
+
+using rm::FrameConst;
+using rm::RowPart;
+using namespace rmhost;
+
+namespace {
+
+// The queue for a W x H frame on the context's stream.  One buffer per context
+// (bloom's rule, rm_capi.cpp bloom_scratch): a refine on another stream than
+// the last one first waits, on the device, for that one, marked when the
+// context left its stream (rm_ctx_streams.cpp set_stream).
+rm_status aa_scratch(rm_ctx *ctx, int W, int H) {
+    if (ctx->aa_ev && ctx->aa_stream != ctx->stream) RM_HIP(hipStreamWaitEvent(ctx->stream, ctx->aa_ev, 0));
+    const size_t words = (size_t)rm::kAaHeadWords + (size_t)W * H;
+    if (words > ctx->aa_words) {
+        if (ctx->aa_queue) RM_HIP(hipFree(ctx->aa_queue));  // (waits for the launches that use it)
+        ctx->aa_queue = nullptr;
+        ctx->aa_words = 0;
+        RM_HIP(hipMalloc(&ctx->aa_queue, words * sizeof(uint32_t)));
+        ctx->aa_words = words;
+    }
+    return RM_OK;
+}
+
+// detect, then refine, on the context's stream; device pointers
+rm_status refine_dev(rm_ctx *ctx, int W, int H, const rm_aa_params &p, uint32_t *frame, uint8_t *mask,
+                     rm_aa_stats *stats) {
+    rm::TraceRange range("rm_refine");
+    if (rm_status st = aa_scratch(ctx, W, H)) return st;
+    uint32_t *count = ctx->aa_queue, *queue = ctx->aa_queue + rm::kAaHeadWords;
+    RowPart part;
+    (void)rm::band_part(H, 1, 0, part);  // the whole frame, as rm_render_rgba8's launch
+    const FrameConst F = frame_const(ctx, W, H, part, H);
+    if (stats && !ctx->aa_ev2) RM_HIP(hipEventCreate(&ctx->aa_ev2));
+    RM_HIP(hipMemsetAsync(count, 0, sizeof(uint32_t), ctx->stream));
+    if (stats) RM_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+    hipError_t e = rm::launch_aa_detect(frame, W, H, p.threshold, mask, count, queue, ctx->stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "supersampling detect launch");
+    ctx->aa_stream = ctx->stream;
+    ctx->aa_pending = true;
+    mark_done(ctx);
+    if (stats) RM_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+    const int layout = rm::aa_layout();
+    e = ctx->scene == rm::SCENE_S0 || ctx->scene == rm::SCENE_T
+            ? rm::launch_aa_refine_t(ctx->scene, F, p.samples, layout, count, queue, frame, ctx->stream)
+            : rm::launch_aa_refine_o(ctx->scene, F, p.samples, layout, count, queue, frame, ctx->stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "supersampling refine launch");
+    if (stats) {
+        RM_HIP(hipEventRecord(ctx->aa_ev2, ctx->stream));
+        RM_HIP(hipEventSynchronize(ctx->aa_ev2));
+        uint32_t n = 0;
+        RM_HIP(hipMemcpy(&n, count, sizeof(n), hipMemcpyDeviceToHost));
+        stats->refined = (int64_t)n;
+        RM_HIP(hipEventElapsedTime(&stats->detect_ms, ctx->ev0, ctx->ev1));
+        RM_HIP(hipEventElapsedTime(&stats->refine_ms, ctx->ev1, ctx->aa_ev2));
+    }
+    return RM_OK;
+}
+
+// the checks of both calls, before any pointer is used
+rm_status aa_check(rm_ctx *ctx, const char *what, int W, int H, const rm_aa_params *p, const uint32_t *frame) {
+    if (W <= 0 || H <= 0 || (int64_t)W * H >= rmaa::kMaxPixels || !p || !frame)
+        return fail(ctx, RM_ERR_INVALID_ARGUMENT, std::string(what) + ": bad arguments");
+    if (!rmaa::samples_ok(p->samples) || !rmaa::threshold_ok(p->threshold))
+        return fail(ctx, RM_ERR_INVALID_ARGUMENT, std::string(what) + ": samples must be 2, 4 or 8 and threshold 0..255");
+    if (ctx->scene < 0) return fail(ctx, RM_ERR_NO_SCENE, "no scene loaded (rm_load_scene)");
+    if (ctx->scene == rm::SCENE_PLUGIN) return fail(ctx, RM_ERR_SCENE, "adaptive supersampling: built-in scenes only");
+    return RM_OK;
+}
+
+// render: rm_render_rgba8 into the frame first (rm_render_aa_rgba8)
+rm_status aa_run(rm_ctx *ctx, const char *what, int W, int H, const rm_aa_params *p, uint32_t *frame, uint8_t *mask,
+                 rm_aa_stats *stats, bool render) {
+    if (!ctx) return RM_ERR_INVALID_ARGUMENT;
+    if (rm_status st = aa_check(ctx, what, W, H, p, frame)) return st;
+    RM_HIP(hipSetDevice(ctx->device));
+    const bool dev = is_device_ptr(frame);
+    if (mask && is_device_ptr(mask) != dev)
+        return fail(ctx, RM_ERR_INVALID_ARGUMENT, std::string(what) + ": host and device pointers mixed");
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    const size_t px = (size_t)W * H, frame_bytes = px * sizeof(uint32_t);
+    char *tmp = nullptr;
+    if (!dev) RM_HIP(hipMalloc(&tmp, frame_bytes + (mask ? px : 0)));  // host buffers: staged
+    uint32_t *frame_d = dev ? frame : reinterpret_cast<uint32_t *>(tmp);
+    uint8_t *mask_d = dev || !mask ? mask : reinterpret_cast<uint8_t *>(tmp + frame_bytes);
+    rm_status st = RM_OK;
+    hipError_t e = hipSuccess;
+    if (render) {
+        rm_stats base;
+        st = render_any(ctx, W, H, H, 1, 0, 0, -1, frame_d, true, stats ? &base : nullptr);
+        if (st == RM_OK && stats) stats->base_ms = base.kernel_ms;
+    } else if (!dev) {
+        e = hipMemcpyAsync(frame_d, frame, frame_bytes, hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) st = hip_fail(ctx, e, "supersampling: staging");
+    }
+    if (st == RM_OK) st = refine_dev(ctx, W, H, *p, frame_d, mask_d, stats);
+    if (!dev) {
+        if (st == RM_OK) {
+            e = hipMemcpyAsync(frame, frame_d, frame_bytes, hipMemcpyDeviceToHost, ctx->stream);
+            if (e == hipSuccess && mask) e = hipMemcpyAsync(mask, mask_d, px, hipMemcpyDeviceToHost, ctx->stream);
+            if (e != hipSuccess) st = hip_fail(ctx, e, "supersampling: staging");
+        }
+        e = hipStreamSynchronize(ctx->stream);  // (also after a failure: tmp may be in use)
+        if (st == RM_OK && e != hipSuccess) st = hip_fail(ctx, e, what);
+        (void)hipFree(tmp);
+    }
+    return st;
+}
+
+}  // namespace
+
+extern "C" {
+
+rm_status rm_refine_rgba8(rm_ctx *ctx, int W, int H, const rm_aa_params *params, uint32_t *frame, uint8_t *mask,
+                          rm_aa_stats *stats) {
+    return aa_run(ctx, "rm_refine_rgba8", W, H, params, frame, mask, stats, false);
+}
+
+rm_status rm_render_aa_rgba8(rm_ctx *ctx, int W, int H, const rm_aa_params *params, uint32_t *out, uint8_t *mask,
+                             rm_aa_stats *stats) {
+    return aa_run(ctx, "rm_render_aa_rgba8", W, H, params, out, mask, stats, true);
+}
+
+}  // extern "C"

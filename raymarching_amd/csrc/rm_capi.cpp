@@ -100,6 +100,9 @@ rm_status rm_destroy(rm_ctx *ctx) {
     if (ctx->staging) (void)hipFree(ctx->staging);
     if (ctx->mips) (void)hipFree(ctx->mips);
     if (ctx->bloom_ev) (void)hipEventDestroy(ctx->bloom_ev);
+    if (ctx->aa_queue) (void)hipFree(ctx->aa_queue);
+    if (ctx->aa_ev) (void)hipEventDestroy(ctx->aa_ev);
+    if (ctx->aa_ev2) (void)hipEventDestroy(ctx->aa_ev2);
     if (ctx->tile_order) (void)hipFree(ctx->tile_order);
     for (rm_ctx::Sched &e : ctx->sched) (void)sched_release(ctx, e);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);

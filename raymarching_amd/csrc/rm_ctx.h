@@ -73,6 +73,16 @@ struct rm_ctx {
     hipEvent_t bloom_ev = nullptr;
     hipStream_t bloom_stream = nullptr;
     bool bloom_pending = false;  // a bloom ran on bloom_stream since bloom_ev was last recorded
+    // adaptive supersampling's queue (rm_aa.h: the count's line, then a word per
+    // pixel): one per context, grown on demand, with bloom's stream rule -- aa_ev
+    // is recorded when the context leaves the stream of its last refine, and a
+    // refine on another stream first waits for it
+    uint32_t *aa_queue = nullptr;
+    size_t aa_words = 0;
+    hipEvent_t aa_ev = nullptr;
+    hipStream_t aa_stream = nullptr;
+    bool aa_pending = false;
+    hipEvent_t aa_ev2 = nullptr;  // a third timing event (rm_aa_stats: detect | refine), made on first use
     rmplugin::Module plugin;  // the loaded scene plugin (scene == SCENE_PLUGIN)
     // the uniforms the loaded scene declares itself (empty for a built-in
     // scene) and their current values, the block every plugin launch passes by

@@ -190,6 +190,13 @@ rm_status set_stream(rm_ctx *ctx, hipStream_t s) {
         RM_HIP(hipEventRecord(ctx->bloom_ev, ctx->stream));
         ctx->bloom_pending = false;
     }
+    if (s != ctx->stream && ctx->aa_pending && ctx->aa_stream == ctx->stream) {
+        // the same for the last refine's queue (rm_aa_host.cpp aa_scratch)
+        RM_HIP(hipSetDevice(ctx->device));
+        if (!ctx->aa_ev) RM_HIP(hipEventCreateWithFlags(&ctx->aa_ev, hipEventDisableTiming));
+        RM_HIP(hipEventRecord(ctx->aa_ev, ctx->stream));
+        ctx->aa_pending = false;
+    }
 #ifdef RM_ANALYSIS_LEAVE_NO_RECORD
     // analysis builds only (-DRM_ANALYSIS_LEAVE_NO_RECORD, tools/scale_model.py
     // prices the marker with it; unsafe: a later release of a schedule buffer or
