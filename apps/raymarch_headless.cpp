@@ -19,6 +19,13 @@
 //          [--post] [--post-sample fxaa|chromatic|texel]
 //          [--tonemap none|aces|reinhard|jodie|uncharted2]
 //          [--uniform name=v[,v...]]... [--pick X,Y] [--aa K[:threshold]]
+//          [--fisheye fov_deg]
+// --fisheye fov_deg writes --ppm from the fisheye camera main() carries
+// commented out (output_shader.frag:396-400) instead of the pinhole's frame:
+// after the last frame its w x h rays are built here on the host, from the
+// last frame's u_pos and u_mouse, and shaded by rm::Shader::shadeRays (rm.h
+// rm_shade_rays) as a ray image with the frame's vignette into RGBA8 words.
+// One GPU.
 // --aa K[:threshold] draws each frame with adaptive supersampling
 // (rm::RenderTexture::drawAA -> rm_render_aa_rgba8): K = 2, 4 or 8 samples at
 // the pixels whose 3x3 neighbourhood spreads a colour channel by at least
@@ -62,6 +69,7 @@ int main(int argc, char** argv) {
     int warmup = 0;
     int pick_x = -1, pick_y = -1;
     int aa_samples = 0, aa_threshold = 32;  // --aa (0: off)
+    float fisheye_fov = 0.0f;               // --fisheye (0: off)
     bool post = false;
     rm_post_sample post_sample = RM_POST_SAMPLE_FXAA;
     rm_tonemap tonemap = RM_TONEMAP_NONE;
@@ -138,6 +146,13 @@ int main(int argc, char** argv) {
                 return 2;
             }
         }
+        else if (a == "--fisheye") {
+            fisheye_fov = (float)std::atof(next().c_str());
+            if (!(fisheye_fov > 0.0f && fisheye_fov <= 360.0f)) {
+                std::fprintf(stderr, "--fisheye fov_deg  (0 < fov <= 360)\n");
+                return 2;
+            }
+        }
         else if (a == "--uniform") {
             const std::string u = next();
             const size_t eq = u.find('=');
@@ -184,6 +199,10 @@ int main(int argc, char** argv) {
     }
     if (aa_samples && (gpus > 1 || sharded || accumulate || fmt_float)) {
         std::fprintf(stderr, "--aa draws on the one-GPU RGBA8 target, without --accumulate\n");
+        return 2;
+    }
+    if (fisheye_fov > 0.0f && (gpus > 1 || sharded || ppm.empty())) {
+        std::fprintf(stderr, "--fisheye writes --ppm, on one GPU\n");
         return 2;
     }
     // one shader (librm context) per GPU; the first is the reference's `shader`
@@ -255,6 +274,7 @@ int main(int argc, char** argv) {
     auto t0 = std::chrono::steady_clock::now();
     auto t_timed = t0;
     double kernel_ms = 0.0;
+    rm::Vec2 mouse{0.0f, 0.0f};  // the last frame's u_mouse
     for (int f = 0; f < warmup + frames; f++) {
         if (f == warmup) {  // the timed frames start when the warm-up frames are done
             if (rm_synchronize(shader.ctx()) != RM_OK) return 1;
@@ -280,7 +300,8 @@ int main(int argc, char** argv) {
         for (bool b : wasd)
             if (b) framesStill = 1;
         setAll("u_pos", pos);
-        setAll("u_mouse", rm::Vec2{mx, my});
+        mouse = rm::Vec2{mx, my};
+        setAll("u_mouse", mouse);
         if (!time_freeze) {
             float t = std::chrono::duration<float>(std::chrono::steady_clock::now() - t0).count();
             setAll("u_time", t);
@@ -352,7 +373,38 @@ int main(int argc, char** argv) {
     }
     if (!ppm.empty()) {
         std::vector<uint32_t> px;
-        if (!sharded ? !outputTexture.copyToHostRGBA8(shader, px) : !shardedTexture.copyToHostRGBA8(px)) return 1;
+        if (fisheye_fov > 0.0f) {
+            // (0, 0, -1) turned by -uv.y and uv.x times radians(fov) / 2, then by the mouse
+            // (output_shader.frag:396-404), in f32; row vector times rot(a) = mat2(c, -s, s, c)
+            auto rot = [](float& a, float& b, float angle) {
+                const float c = std::cos(angle), s = std::sin(angle);
+                const float a1 = a * c + b * -s, b1 = a * s + b * c;
+                a = a1;
+                b = b1;
+            };
+            const float coeff = fisheye_fov * 0.017453292519943295f * 0.5f;
+            std::vector<rm::Vec3> dirs((size_t)w * h);
+            for (int y = 0; y < h; y++) {
+                for (int x = 0; x < w; x++) {
+                    const float ux = (((float)x + 0.5f) / wf - 0.5f) * wf / hf;
+                    const float uy = (((float)y + 0.5f) / hf - 0.5f) * hf / hf;
+                    rm::Vec3 d{0.0f, 0.0f, -1.0f};
+                    rot(d.y, d.z, -uy * coeff);
+                    rot(d.x, d.z, ux * coeff);
+                    rot(d.y, d.z, -mouse.y);
+                    rot(d.x, d.z, mouse.x);
+                    dirs[(size_t)y * w + x] = d;
+                }
+            }
+            px.resize((size_t)w * h);
+            const rm_shade_params sp{w, RM_SHADE_DISPLAY, 1};
+            if (!shader.shadeRays(&pos, true, dirs.data(), (std::int64_t)w * h, sp, nullptr, px.data())) {
+                std::fprintf(stderr, "--fisheye failed: %s\n", shader.lastError().c_str());
+                return 1;
+            }
+        } else if (!sharded ? !outputTexture.copyToHostRGBA8(shader, px) : !shardedTexture.copyToHostRGBA8(px)) {
+            return 1;
+        }
         FILE* fp = std::fopen(ppm.c_str(), "wb");
         if (!fp) return 1;
         std::fprintf(fp, "P6\n%d %d\n255\n", w, h);

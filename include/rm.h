@@ -213,6 +213,58 @@ rm_status rm_cast_rays(rm_ctx *ctx, const float *origins, int shared_origin, con
  * frame's depth / normal / material buffers.  W*H <= 2^30. */
 rm_status rm_camera_rays(rm_ctx *ctx, int W, int H, float *origin3, float *directions);
 
+/* Shade caller-supplied rays: the pass's colour, render(ro, rd) of
+ * output_shader.frag:348-385 / template.frag:45-76 (light, AO, soft shadow,
+ * SSS probes, the mirror bounce, refraction, fog), along n rays the caller
+ * built: a fisheye camera, a cube map or panorama, a stereo pair, lens rays,
+ * or a frame's own rays (rm_camera_rays) for its colour before the tonemap.
+ * The rays run the loaded scene's render kernel code, so rm_camera_rays' rays
+ * with the shared origin u_pos, width = W and vignette = 1 give rm_render's /
+ * rm_render_rgba8's frame in every bit.
+ * directions: n xyz triples, used as given; they must be unit vectors (the
+ * render kernels' exact shortcuts rest on that).  origins: with shared_origin
+ * != 0 a HOST pointer to one triple, read during the call, which is the
+ * launch's u_pos (the context's own is not changed); otherwise n triples of
+ * the buffers' kind.  Exactly one of out_rgba (n x 4 floats, alpha 1) and
+ * out_rgba8 (n words in the scene's own pack, as rm_render_rgba8's;
+ * RM_SHADE_DISPLAY only) is non-NULL; ray i goes to out[i], which for a ray
+ * image is out[y * width + x].
+ * A ray whose origin or direction has a non-finite component, or whose
+ * |direction|^2 differs from 1 by more than 1e-4, is not shaded: its output is
+ * (0, 0, 0, 0) or the word 0 (alpha 0 marks it; every shaded ray has alpha 1 /
+ * 255), and it enters no march.
+ * All buffers are device pointers or all are host pointers (the shared origin
+ * aside); a mix is RM_ERR_INVALID_ARGUMENT.  Device: asynchronous on the ctx
+ * stream unless `stats` is given; then the call waits and fills kernel_ms,
+ * pixels = n and scene (evals = 0).  Host: staged, returns when the results
+ * are written.  RM_ERR_INVALID_ARGUMENT: n < 0, n > 2^30; a NULL params,
+ * origins or directions with n > 0; both or neither output; RM_SHADE_LINEAR
+ * with out_rgba8; width < 0 or n % width != 0; vignette = 1 with width = 0 or
+ * with RM_SHADE_LINEAR; an enum value out of range.  No scene:
+ * RM_ERR_NO_SCENE; a scene plugin without render kernels
+ * (RM_PLUGIN_EVAL_ONLY): RM_ERR_SCENE; n = 0: RM_OK, nothing launched (all
+ * checked before any pointer is used).  Uniforms (u_time, a plugin's own),
+ * rm_params.max_steps and shadow_max_steps are the ctx's, read at the call.
+ * Not here: count_evals and step maps, the adaptive tile order and
+ * rm_set_tile_order (the tiles of a ray image run row-major), bands, shards
+ * and the wire, accumulation, bench.py. */
+enum { RM_SHADE_LINEAR = 0, RM_SHADE_DISPLAY = 1 };
+typedef struct rm_shade_params {
+    int32_t width;    /* 0: rays are a list (64 consecutive rays per wave);
+                         > 0: rays are a width x (n / width) image, row 0 first
+                         (n % width == 0), shaded in 8x8 tiles as a frame is   */
+    int32_t output;   /* RM_SHADE_LINEAR: render()'s colour (float target only);
+                         RM_SHADE_DISPLAY: main()'s tonemap -> contrast
+                         (-> vignette) of it, as a frame's pixels               */
+    int32_t vignette; /* DISPLAY only. 0: factor 1 (the factor at texcoord
+                         (0.5, 0.5), which is exactly 1); 1: the ray image's own
+                         (needs width > 0): pixel (x, y)'s texcoord as the
+                         loaded scene's render kernel computes it for a
+                         width x n/width frame                                  */
+} rm_shade_params;
+rm_status rm_shade_rays(rm_ctx *ctx, const float *origins, int shared_origin, const float *directions, int64_t n,
+                        const rm_shade_params *params, float *out_rgba, uint32_t *out_rgba8, rm_stats *stats);
+
 /* Replace sf::Shader::setUniform (include/SFML/Graphics/Shader.hpp:297,306,315)
  * for the names main.cpp sets: u_resolution (2f), u_pos (3f), u_mouse (2f),
  * u_time (1f), u_sample_part (1f), u_seed1/u_seed2 (2f).  The last three are

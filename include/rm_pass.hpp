@@ -121,6 +121,15 @@ public:
                                     reinterpret_cast<const float*>(directions), n, inside ? 1 : 0, &hits,
                                     stats) == RM_OK;
     }
+    // rm.h rm_shade_rays: the pass's colour along any unit rays (a fisheye, a
+    // cube map, a stereo pair, lens rays); exactly one of rgba (n x 4 floats)
+    // and rgba8 (n words) is set.  A shared origin is a host pointer.
+    bool shadeRays(const Vec3* origins, bool sharedOrigin, const Vec3* directions, std::int64_t n,
+                   const rm_shade_params& params, float* rgba, std::uint32_t* rgba8, rm_stats* stats = nullptr) {
+        return ctx_ && rm_shade_rays(ctx_, reinterpret_cast<const float*>(origins), sharedOrigin ? 1 : 0,
+                                     reinterpret_cast<const float*>(directions), n, &params, rgba, rgba8,
+                                     stats) == RM_OK;
+    }
 
 private:
     bool setArray(const char* name, int components, const float* v, std::size_t length) {

@@ -33,7 +33,7 @@ EXPORTS = ("rm_create", "rm_destroy", "rm_load_scene", "rm_set_uniform1f", "rm_s
            "rm_wire_encode", "rm_wire_decode", "rm_scatter_part_rgba8", "rm_wire_decode_parts",
            "rm_set_uniform4f", "rm_set_uniform1i", "rm_set_uniformfv", "rm_uniform_count", "rm_uniform_info_at",
            "rm_get_uniformfv", "rm_get_uniform1i", "rm_cast_rays", "rm_camera_rays",
-           "rm_aa_offsets", "rm_aa_edge_mask", "rm_refine_rgba8", "rm_render_aa_rgba8")
+           "rm_aa_offsets", "rm_aa_edge_mask", "rm_refine_rgba8", "rm_render_aa_rgba8", "rm_shade_rays")
 
 # include/rm.h RM_ABI_VERSION: the struct layouts below
 ABI_VERSION = 3
@@ -96,6 +96,15 @@ class RmAaStats(ctypes.Structure):
 
 
 RAY_STATUS = {0: "miss", 1: "hit", 2: "exhausted"}  # include/rm.h RM_RAY_*
+
+
+class RmShadeParams(ctypes.Structure):
+    """include/rm.h rm_shade_params."""
+    _fields_ = [("width", ctypes.c_int32), ("output", ctypes.c_int32), ("vignette", ctypes.c_int32)]
+
+
+RM_SHADE_LINEAR, RM_SHADE_DISPLAY = 0, 1  # include/rm.h
+SHADE_OUTPUTS = {"linear": RM_SHADE_LINEAR, "display": RM_SHADE_DISPLAY}
 
 
 class RmCommId(ctypes.Structure):
@@ -181,6 +190,8 @@ def lib() -> ctypes.CDLL:
         "rm_aa_edge_mask": ([c.c_int, c.c_int, c.c_int, vp, vp], c.c_int),
         "rm_refine_rgba8": ([vp, c.c_int, c.c_int, c.POINTER(RmAaParams), vp, vp, c.POINTER(RmAaStats)], c.c_int),
         "rm_render_aa_rgba8": ([vp, c.c_int, c.c_int, c.POINTER(RmAaParams), vp, vp, c.POINTER(RmAaStats)], c.c_int),
+        "rm_shade_rays": ([vp, vp, c.c_int, vp, c.c_int64, c.POINTER(RmShadeParams), vp, vp, c.POINTER(RmStats)],
+                          c.c_int),
         "rm_sharded_layout": ([c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.POINTER(RmShardLayout)], c.c_int),
         "rm_comm_get_id": ([c.POINTER(RmCommId)], c.c_int),
         "rm_comm_init_rank": ([c.POINTER(vp), vp, c.c_int, c.POINTER(RmCommId), c.c_int], c.c_int),

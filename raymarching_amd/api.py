@@ -548,6 +548,60 @@ class Renderer:
         check(lib().rm_camera_rays(self._ctx, int(W), int(H), self._ptr(origin), self._ptr(directions)), self._ctx)
         return origin, directions
 
+    def shade_rays(self, origins, directions, width: int = 0, output: str = "display", vignette: bool = False,
+                   rgba8: bool = False, out=None, stats: bool = False, normalize: bool = False):
+        """rm_shade_rays: the pass's colour (render(ro, rd): light, AO, soft
+        shadow, SSS, reflection, refraction, fog) along rays directions [..., 3]
+        (unit vectors; normalize=True normalises them in f32 first) from
+        origins [n, 3], or [3] for one origin shared by all rays (the launch's
+        u_pos).  width > 0: the rays are a width x (n / width) image, shaded in
+        8x8 tiles; 0: a list.  output "linear" (render()'s colour) or "display"
+        (tonemap -> contrast, times the ray image's vignette with
+        vignette=True, as a frame's pixels).  Returns [n, 4] f32 (alpha 1), or
+        [n] RGBA8 words with rgba8=True; a ray that is not a finite unit ray
+        gives zeros (alpha 0).  numpy arrays: staged, a numpy result.  torch
+        tensors on this renderer's device: a device tensor, asynchronous on the
+        renderer's stream (unless stats=True).  camera_rays' rays with
+        width=W, vignette=True give render(W, H) / render_rgba8(W, H) bit for
+        bit.  -> colours[, stats]."""
+        import numpy as np
+        if output not in _lib.SHADE_OUTPUTS:
+            raise ValueError(f"shade_rays: output {output!r}; expected one of {sorted(_lib.SHADE_OUTPUTS)}")
+        on_device = hasattr(directions, "data_ptr") and directions.is_cuda
+        if on_device:
+            torch = _torch()
+            d = directions.to(torch.float32).reshape(-1, 3)
+            if normalize:
+                d = d / torch.linalg.vector_norm(d, dim=1, keepdim=True)
+            d = d.contiguous()
+            o = torch.as_tensor(origins, dtype=torch.float32)
+            # (the shared origin is read on the host; origins per ray live where the directions do)
+            o = (o.cpu() if o.ndim == 1 else o.to(d.device)).contiguous()
+        else:
+            d = np.ascontiguousarray(np.asarray(directions), np.float32).reshape(-1, 3)
+            if normalize:
+                d = d / np.sqrt((d * d).sum(1, dtype=np.float32, keepdims=True), dtype=np.float32)
+            if hasattr(origins, "data_ptr"):
+                origins = origins.cpu().numpy()
+            o = np.ascontiguousarray(np.asarray(origins), np.float32)
+        n = len(d)
+        shared = o.ndim == 1
+        if tuple(o.shape) != ((3,) if shared else (n, 3)):
+            raise ValueError(f"shade_rays: origins {tuple(o.shape)} for {n} directions; expected [3] or [{n}, 3]")
+        if out is None:
+            if on_device:
+                out = torch.empty((n,) if rgba8 else (n, 4), dtype=torch.int32 if rgba8 else torch.float32,
+                                  device=d.device)
+            else:
+                out = np.empty((n,) if rgba8 else (n, 4), np.uint32 if rgba8 else np.float32)
+        _check_out(out, n if rgba8 else 4 * n)
+        p = _lib.RmShadeParams(int(width), _lib.SHADE_OUTPUTS[output], int(bool(vignette)))
+        s = RmStats()
+        check(lib().rm_shade_rays(self._ctx, self._ptr(o), int(shared), self._ptr(d), n, ctypes.byref(p),
+                                  None if rgba8 else self._ptr(out), self._ptr(out) if rgba8 else None,
+                                  ctypes.byref(s) if stats else None), self._ctx)
+        return (out, s.as_dict()) if stats else out
+
     def render_rgba8(self, W, H, out=None, stats=False):
         torch = _torch()
         if out is None:

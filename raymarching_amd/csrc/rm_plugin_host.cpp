@@ -290,6 +290,10 @@ hipError_t load(const Code& code, int uniform_slots, Module& m) {
         (void)hipGetLastError();
         n.render = n.render_count = nullptr;
     }
+    if (!n.render || hipModuleGetFunction(&n.shade, n.mod, "rm_plugin_shade") != hipSuccess) {
+        (void)hipGetLastError();
+        n.shade = nullptr;
+    }
     e = hipModuleGetFunction(&n.eval, n.mod, "rm_plugin_eval");
     if (e == hipSuccess) e = hipModuleGetFunction(&n.cast, n.mod, "rm_plugin_cast");
     if (e != hipSuccess) {
@@ -351,6 +355,19 @@ hipError_t launch_cast(const Module& m, const rm::FrameConst& F, const uint32_t*
     void* with_block[] = {&f, const_cast<uint32_t*>(uniforms), &q, &in};
     void* args[] = {&f, &q, &in};
     return hipModuleLaunchKernel(m.cast, (unsigned)((Q.n + block - 1) / block), 1, 1, (unsigned)block, 1, 1, 0, s,
+                                 m.uniform_slots > 0 ? with_block : args, nullptr);
+}
+
+hipError_t launch_shade(const Module& m, const rm::FrameConst& F, const uint32_t* uniforms, const rm::ShadeRays& Q,
+                        hipStream_t s) {
+    if (!m.shade) return hipErrorInvalidDeviceFunction;
+    if (Q.n <= 0) return hipSuccess;
+    rm::FrameConst f = F;
+    rm::ShadeRays q = Q;
+    // (the uniform block is read now, as launch_eval's)
+    void* with_block[] = {&f, const_cast<uint32_t*>(uniforms), &q};
+    void* args[] = {&f, &q};
+    return hipModuleLaunchKernel(m.shade, rm::shade_grid(Q), 1, 1, 64, 1, 1, 0, s,
                                  m.uniform_slots > 0 ? with_block : args, nullptr);
 }
 

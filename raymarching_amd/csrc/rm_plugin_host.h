@@ -9,6 +9,7 @@
 
 #include "rm_device.h"
 #include "rm_rays.h"
+#include "rm_shade.h"
 #include "rm_uniform_decl.h"
 
 namespace rmplugin {
@@ -39,6 +40,7 @@ struct Module {
     hipFunction_t render_count = nullptr;  // instrumented render kernel (ray-step counts, step maps)
     hipFunction_t eval = nullptr;
     hipFunction_t cast = nullptr;          // rm_cast_rays' march (RM_PLUGIN_EVAL_ONLY scenes have it too)
+    hipFunction_t shade = nullptr;         // rm_shade_rays' kernel; null for an RM_PLUGIN_EVAL_ONLY scene
     Code code;
     int uniform_slots = 0;  // > 0: the kernels take the uniform block as their second argument (rm_plugin.h)
 };
@@ -54,5 +56,8 @@ hipError_t launch_eval(const Module& m, const rm::FrameConst& F, const uint32_t*
 // `block`: threads per workgroup (rm::cast_block_size)
 hipError_t launch_cast(const Module& m, const rm::FrameConst& F, const uint32_t* uniforms, const rm::RayQuery& Q,
                        int inside, int block, hipStream_t s);
+// hipErrorInvalidDeviceFunction for a scene without render kernels (RM_PLUGIN_EVAL_ONLY)
+hipError_t launch_shade(const Module& m, const rm::FrameConst& F, const uint32_t* uniforms, const rm::ShadeRays& Q,
+                        hipStream_t s);
 
 }  // namespace rmplugin

@@ -7,6 +7,7 @@
 // parameter itself is never named), loaded once at the top of each kernel.
 #pragma once
 #include "rm_rays.h"
+#include "rm_shade.h"
 
 #ifdef RM_UNIFORM_SLOTS
 #define RM_UNIFORM_PARAM rm::glsl::UniformBlock,
@@ -77,6 +78,14 @@ extern "C" __global__ __launch_bounds__(64) void rm_plugin_render_count(rm::Fram
                                                                          int rgba8, unsigned long long* evals) {
     RM_UNIFORM_PRELOAD();
     rm::plugin_render_tile<true>(F, out, rgba8, evals);
+}
+
+// the pass's colour along caller-supplied rays (rm_shade_rays, rm_shade.h): one
+// kernel (one more copy of the pipeline to compile per scene, not four), the
+// lane layout and the origins' kind read from the launch, wave-uniform
+extern "C" __global__ __launch_bounds__(64) void rm_plugin_shade(rm::FrameConst F, RM_UNIFORM_PARAM rm::ShadeRays Q) {
+    RM_UNIFORM_PRELOAD();
+    rm::shade_rays_one<rm::SCENE_PLUGIN, rm::SHADE_PER_LAUNCH, rm::SHADE_PER_LAUNCH>(F, Q);
 }
 #endif
 

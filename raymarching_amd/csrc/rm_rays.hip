@@ -11,6 +11,7 @@
 #include <cstdlib>
 
 #include "rm_rays.h"
+#include "rm_shade.h"
 
 namespace rm {
 
@@ -22,10 +23,10 @@ __global__ __launch_bounds__(256) void rm_cast_rays_kernel(FrameConst F, RayQuer
     cast_rays_one<SC>(F, Q, inside);
 }
 
-template <bool FAST>
+// (the exact forms: scenes O, OG and plugins)
 __global__ __launch_bounds__(256) void rm_camera_rays_kernel(FrameConst F, float* __restrict__ origin3,
                                                               float* __restrict__ directions) {
-    camera_rays_one<FAST>(F, origin3, directions);
+    camera_rays_one<false>(F, origin3, directions);
 }
 
 // 64 threads; RM_CAST_BLOCK=256 selects four-wave workgroups, read at every
@@ -56,11 +57,14 @@ hipError_t launch_cast_rays(int scene, const FrameConst& F, const RayQuery& Q, i
 }
 
 hipError_t launch_camera_rays(bool fast, const FrameConst& F, float* origin3, float* directions, hipStream_t s) {
+    // the hardware forms (scenes S0/T) under the flags of those scenes' frame kernels, which contract within
+    // expressions (rm_shade_t.hip): the rays are then the frame's own in every bit, and rm_shade_rays of them
+    // its pixels
+    if (fast) return launch_camera_rays_hw(F, origin3, directions, s);
     const long long n = (long long)F.W * F.H;
     if (n <= 0) return hipSuccess;
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    if (fast) hipLaunchKernelGGL((rm_camera_rays_kernel<true>), grid, block, 0, s, F, origin3, directions);
-    else hipLaunchKernelGGL((rm_camera_rays_kernel<false>), grid, block, 0, s, F, origin3, directions);
+    hipLaunchKernelGGL(rm_camera_rays_kernel, grid, block, 0, s, F, origin3, directions);
     return hipGetLastError();
 }
 

@@ -633,16 +633,12 @@ __device__ __forceinline__ V3 render_O(const FrameConst& F, V3 ro, V3 rd, Tally&
 
 // template.frag:45-76 (scene T); NB: sponge_folds; SETTLE: soft_shadow2_T_loop;
 // RSTOP: cast_ray_T's RS for the reflection march
+// render_T_from: the same with the primary ray's sponge-space image given by the
+// caller (rm_shade.h builds it per lane for rays with origins of their own)
 template <int NB = 3, int SETTLE = 0, int RSTOP = 0>
-__device__ __forceinline__ V3 render_T(const FrameConst& F, V3 ro, V3 rd, Tally& cnt) {
+__device__ __forceinline__ V3 render_T_from(const FrameConst& F, const LinRay& prim, V3 ro, V3 rd, Tally& cnt) {
     constexpr int SC = SCENE_T;
     using P = ScenePolicy<SC>;
-    // ro is the camera, u_pos: its sponge-space image is the frame's, F.camq_* (rm_device.h camera_sponge_origin)
-    float qx = F.camq_x, qy = F.camq_y, qz = F.camq_z;
-    // (in VGPRs, as the lanes' own results were: an SGPR addend makes the march's three FMAs per step the slow
-    // issue form, DESIGN.md 2.16)
-    asm volatile("" : "+v"(qx), "+v"(qy), "+v"(qz));
-    const LinRay prim{v3(qx, qy, qz), sponge_rot<P::kExactMarch>(F, rd.x, rd.y, rd.z)};
     V3 p = ro + rd * cast_ray_T<NB>(F, prim, cnt);
     V3 n = normal_fast<SC, NB>(F, p, cnt);
     // getColorReflect (common.frag:991-1002); its dead nr normal is skipped
@@ -679,6 +675,16 @@ __device__ __forceinline__ V3 render_T(const FrameConst& F, V3 ro, V3 rd, Tally&
     shading = shading + v3(0.40f, 0.28f, 0.20f) * ind * occ;
     shading = shading + v3s(fre * occ);
     return apply_scattering<P::kTrim>(v3s(c) * shading, ro, p);
+}
+template <int NB = 3, int SETTLE = 0, int RSTOP = 0>
+__device__ __forceinline__ V3 render_T(const FrameConst& F, V3 ro, V3 rd, Tally& cnt) {
+    // ro is the camera, u_pos: its sponge-space image is the frame's, F.camq_* (rm_device.h camera_sponge_origin)
+    float qx = F.camq_x, qy = F.camq_y, qz = F.camq_z;
+    // (in VGPRs, as the lanes' own results were: an SGPR addend makes the march's three FMAs per step the slow
+    // issue form, DESIGN.md 2.16)
+    asm volatile("" : "+v"(qx), "+v"(qy), "+v"(qz));
+    const LinRay prim{v3(qx, qy, qz), sponge_rot<ScenePolicy<SCENE_T>::kExactMarch>(F, rd.x, rd.y, rd.z)};
+    return render_T_from<NB, SETTLE, RSTOP>(F, prim, ro, rd, cnt);
 }
 
 // BASELINE config-1 scene S0: castRayD + normal + lambert
