@@ -23,6 +23,7 @@ using __hip_internal::uint64_t;
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #endif
+#include "rm_far_sky.h"
 
 namespace rm {
 
@@ -69,7 +70,11 @@ struct FrameConst {
     uint32_t gx_magic;             // floor(t / tiles_x) = umulhi(t, gx_magic) for every tile t, or 0: divide
     float camq_x, camq_y, camq_z;  // sponge_space<false>(u_pos): the primary rays' origin in sponge space (scene T),
                                    // the same FMAs in the same order on the host (camera_sponge_origin)
+    int far_sky;                   // scene T with max_steps >= rmfs::kFarSkyN0: waves whose rays all pass
+                                   // rmfs::far_sky_ray skip the primary and the reflection march (rm_far_sky.h;
+                                   // in the struct's tail padding: no other member moves)
 };
+static_assert(rmfs::kFarSkyDepth == ZFAR, "rm_far_sky.h restates ZFAR");
 
 // FrameConst.camq_*: sponge_space<false>(F, u_pos) below, FMA for FMA (each one
 // rounding, on the host as on the device), so that scene T's lanes do not each
@@ -139,6 +144,8 @@ struct ScenePolicy {
     static constexpr bool kPlaneSpans = SC == SCENE_O || SC == SCENE_OG;
     static constexpr bool kProbeFma = kPlaneSpans;
     static constexpr bool kSettleO = kPlaneSpans;
+    // Scene T: the far-sky shortcut of render_T_from (rm_far_sky.h)
+    static constexpr bool kFarSky = SC == SCENE_T;
     // Minimum waves per SIMD the register allocator must allow.  Scene O asks
     // for 8 (64 VGPRs): its kernel needs ~82, and the few spills to scratch cost
     // less than occupancy 5 does (C5 frame 12.29 -> 11.56 ms,

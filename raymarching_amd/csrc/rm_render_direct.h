@@ -632,23 +632,45 @@ __device__ __forceinline__ V3 render_O(const FrameConst& F, V3 ro, V3 rd, Tally&
 }
 
 // template.frag:45-76 (scene T); NB: sponge_folds; SETTLE: soft_shadow2_T_loop;
-// RSTOP: cast_ray_T's RS for the reflection march
+// RSTOP: cast_ray_T's RS for the reflection march, and the far-sky shortcut's mode (below)
 // render_T_from: the same with the primary ray's sponge-space image given by the
 // caller (rm_shade.h builds it per lane for rays with origins of their own)
 template <int NB = 3, int SETTLE = 0, int RSTOP = 0>
 __device__ __forceinline__ V3 render_T_from(const FrameConst& F, const LinRay& prim, V3 ro, V3 rd, Tally& cnt) {
     constexpr int SC = SCENE_T;
     using P = ScenePolicy<SC>;
-    V3 p = ro + rd * cast_ray_T<NB>(F, prim, cnt);
+    // The far-sky shortcut (rm_far_sky.h states the proof): in a wave whose active lanes all pass
+    // far_sky_ray the primary march returns ZFAR and the reflection factor is 1, on every lane, whatever their
+    // steps.  Decided per wave (a scalar branch: a mixed wave marches as before), with RSTOP's modes: 1 (timed
+    // kernels) takes neither march, 2 (instrumented) takes both and counts all their steps in cnt.skipped.
+    bool far = false;
+    if constexpr (P::kFarSky && RSTOP != 0) {
+        if (F.far_sky)
+            far = __builtin_amdgcn_ballot_w64(
+                      rmfs::far_sky_ray(prim.o.x, prim.o.y, prim.o.z, prim.d.x, prim.d.y, prim.d.z)) ==
+                  __builtin_amdgcn_ballot_w64(true);  // (every active lane)
+    }
+    const uint32_t e0 = cnt.evals;
+    float depth = ZFAR;
+    if (RSTOP != 1 || !far) depth = cast_ray_T<NB>(F, prim, cnt);
+    if constexpr (RSTOP == 2) cnt.skipped += far ? cnt.evals - e0 : 0u;
+    V3 p = ro + rd * depth;
     V3 n = normal_fast<SC, NB>(F, p, cnt);
-    // getColorReflect (common.frag:991-1002); its dead nr normal is skipped
-    V3 rdir = reflect(rd, n);
-    V3 ror = p + rdir * 0.01f;
-    V3 pr = ror + rdir * cast_ray_T<NB, RSTOP>(F, sponge_ray(F, ror, rdir), cnt);
-    // |pr - p| >= 0.01 (the offset of ror; the march adds depth >= ZNEAR along rdir): far above 2^-96, below
-    // which alone sqrtf's rescaling acts, so the bare v_sqrt_f32 is length()'s float (apply_scattering, TRIM)
-    const V3 pd = pr - p;
-    float c = clamp01_as<P::kTrim>(__builtin_amdgcn_sqrtf(dot(pd, pd)) * (1.0f / 3.0f));
+    float c = 1.0f;
+    if (RSTOP != 1 || !far) {
+        // getColorReflect (common.frag:991-1002); its dead nr normal is skipped
+        const uint32_t e1 = cnt.evals, s1 = cnt.skipped;
+        V3 rdir = reflect(rd, n);
+        V3 ror = p + rdir * 0.01f;
+        V3 pr = ror + rdir * cast_ray_T<NB, RSTOP>(F, sponge_ray(F, ror, rdir), cnt);
+        if constexpr (RSTOP == 2) cnt.skipped = far ? s1 + (cnt.evals - e1) : cnt.skipped;
+        (void)e1; (void)s1;
+        // |pr - p| >= 0.01 (the offset of ror; the march adds depth >= ZNEAR along rdir): far above 2^-96, below
+        // which alone sqrtf's rescaling acts, so the bare v_sqrt_f32 is length()'s float (apply_scattering, TRIM)
+        const V3 pd = pr - p;
+        c = clamp01_as<P::kTrim>(__builtin_amdgcn_sqrtf(dot(pd, pd)) * (1.0f / 3.0f));
+    }
+    (void)e0;
     const V3 lightPos = v3(20.0f, 50.0f, 0.0f);
     V3 Ld = lightPos - p;
     float ld2 = dot(Ld, Ld);

@@ -127,6 +127,8 @@ FrameConst frame_const(const rm_ctx *c, int W, int H, const RowPart &part, int n
     F.max_steps = c->params.max_steps;
     // 0 (unbounded, the reference) travels as INT_MAX: one compare per shadow step
     F.shadow_max_steps = c->params.shadow_max_steps > 0 ? c->params.shadow_max_steps : 0x7fffffff;
+    // the far-sky shortcut's proof needs max_steps >= N0 (rm_far_sky.h); any other step cap marches every ray
+    F.far_sky = c->scene == rm::SCENE_T && F.max_steps >= rmfs::kFarSkyN0 ? 1 : 0;
     F.lat_tiles = lat_tiles_for(pick_kernel(c->params), W, nrows);
     for (int i = 0; i < 32; i++) {
         F.hash11[i] = hash11((float)i);
