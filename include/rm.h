@@ -168,6 +168,25 @@ rm_status rm_compile_scene(const char *file_name, char *log, size_t log_size);
  * returns when the results are written.  Uniforms (u_time ...) are the ctx's. */
 rm_status rm_scene_eval(rm_ctx *ctx, const float *points, int64_t n, float *dist, float *material);
 
+/* The same in one of the forms a scene distance has.  RM_FORM_EXACT is
+ * rm_scene_eval's kernel: the reference's arithmetic, the form of marches and
+ * normals.  RM_FORM_PROBE is the form of the ambient-occlusion, soft-shadow and
+ * thickness probes and of all of scene T's marches: fused and reciprocal
+ * arithmetic, within ~1e-5 of the exact form, not its bits (a plugin's: its
+ * sceneSDF over the scene library's probe instance).  RM_FORM_PROBE_NB1 is the
+ * probe form with one fold exit test instead of three, which scene T's latency
+ * tiles run; the same kernel as RM_FORM_PROBE for every other scene.
+ * material (NULL or n x 16): as rm_scene_eval's; a plugin's comes from the
+ * instance of the scene library that `form` names.  aux (NULL or n floats):
+ * for the compiled-in scene O (and its glass variant) the probe form's slack
+ * at the point, which certifies that the scene is its floor plane within that
+ * distance (the renderer replaces ray spans and probe sets by the plane where
+ * it is large enough); 0 for every other scene.  A form outside the enum:
+ * RM_ERR_INVALID_ARGUMENT. */
+typedef enum rm_form { RM_FORM_EXACT = 0, RM_FORM_PROBE = 1, RM_FORM_PROBE_NB1 = 2 } rm_form;
+rm_status rm_scene_eval_form(rm_ctx *ctx, const float *points, int64_t n, int form, float *dist, float *material,
+                             float *aux);
+
 /* Ray queries: castRayD (common.frag:879-901; castRayDI, :903-925, when
  * inside != 0) of the loaded scene along n caller-supplied rays, the march the
  * render kernels run first for every pixel, on its own: picking, camera

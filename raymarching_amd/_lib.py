@@ -33,7 +33,7 @@ EXPORTS = ("rm_create", "rm_destroy", "rm_load_scene", "rm_set_uniform1f", "rm_s
            "rm_wire_encode", "rm_wire_decode", "rm_scatter_part_rgba8", "rm_wire_decode_parts",
            "rm_set_uniform4f", "rm_set_uniform1i", "rm_set_uniformfv", "rm_uniform_count", "rm_uniform_info_at",
            "rm_get_uniformfv", "rm_get_uniform1i", "rm_cast_rays", "rm_camera_rays",
-           "rm_aa_offsets", "rm_aa_edge_mask", "rm_refine_rgba8", "rm_render_aa_rgba8", "rm_shade_rays")
+           "rm_aa_offsets", "rm_aa_edge_mask", "rm_refine_rgba8", "rm_render_aa_rgba8", "rm_shade_rays", "rm_scene_eval_form")
 
 # include/rm.h RM_ABI_VERSION: the struct layouts below
 ABI_VERSION = 3
@@ -184,6 +184,7 @@ def lib() -> ctypes.CDLL:
                                        c.POINTER(RmStats)], c.c_int),
         "rm_compile_scene": ([cp, vp, c.c_size_t], c.c_int),
         "rm_scene_eval": ([vp, vp, c.c_int64, vp, vp], c.c_int),
+        "rm_scene_eval_form": ([vp, vp, c.c_int64, c.c_int, vp, vp, vp], c.c_int),
         "rm_cast_rays": ([vp, vp, c.c_int, vp, c.c_int64, c.c_int, c.POINTER(RmRayHits), c.POINTER(RmStats)], c.c_int),
         "rm_camera_rays": ([vp, c.c_int, c.c_int, vp, vp], c.c_int),
         "rm_aa_offsets": ([c.c_int, vp], c.c_int),

@@ -479,17 +479,33 @@ class Renderer:
                   self._ctx)
         return mid, out
 
-    def scene_eval(self, points, material: bool = False):
+    SCENE_FORMS = {"exact": 0, "probe": 1, "probe_nb1": 2}  # rm.h rm_form
+
+    def scene_eval(self, points, material: bool = False, form: str = "exact", aux: bool = False):
         """sceneSDF(p) of the loaded scene at points [n, 3] (host, numpy):
-        dist [n], and with material=True also the [n, 16] Material floats."""
+        dist [n], and with material=True also the [n, 16] Material floats.
+        form: "exact" (rm_scene_eval), "probe" or "probe_nb1"
+        (rm_scene_eval_form: the probe form of the distance; with one fold exit
+        test).  aux=True appends the [n] floats of rm_scene_eval_form's aux
+        (the compiled-in scene O's probe-form slack, 0 for other scenes).
+        Returns dist, or the tuple (dist[, material][, aux])."""
         import numpy as np
+        if form not in self.SCENE_FORMS:
+            raise ValueError(f"form must be one of {sorted(self.SCENE_FORMS)}, not {form!r}")
         pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
         n = len(pts)
         dist = np.zeros(n, np.float32)
         mat = np.zeros((n, 16), np.float32) if material else None
-        check(lib().rm_scene_eval(self._ctx, self._ptr(pts), n, self._ptr(dist),
-                                  self._ptr(mat) if material else None), self._ctx)
-        return (dist, mat) if material else dist
+        ax = np.zeros(n, np.float32) if aux else None
+        if form == "exact" and not aux:
+            check(lib().rm_scene_eval(self._ctx, self._ptr(pts), n, self._ptr(dist),
+                                      self._ptr(mat) if material else None), self._ctx)
+        else:
+            check(lib().rm_scene_eval_form(self._ctx, self._ptr(pts), n, self.SCENE_FORMS[form], self._ptr(dist),
+                                           self._ptr(mat) if material else None, self._ptr(ax) if aux else None),
+                  self._ctx)
+        out = (dist,) + ((mat,) if material else ()) + ((ax,) if aux else ())
+        return out if len(out) > 1 else dist
 
     def cast_rays(self, origins, directions, inside: bool = False, normal: bool = True, material: bool = False,
                   stats: bool = False) -> dict:

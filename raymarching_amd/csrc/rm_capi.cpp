@@ -760,32 +760,65 @@ rm_status rm_post_chain_ex(rm_ctx *ctx, int W, int H, int sample, int tonemap, c
     return RM_OK;
 }
 
-rm_status rm_scene_eval(rm_ctx *ctx, const float *points, int64_t n, float *dist, float *material) {
+// rm_scene_eval and rm_scene_eval_form.  RM_FORM_EXACT launches rm_scene_eval's
+// kernel (and, for aux alone, the probe kernel without its other outputs).
+static rm_status scene_eval_form(rm_ctx *ctx, const float *points, int64_t n, int form, float *dist, float *material,
+                                 float *aux, const char *what) {
     if (!ctx) return RM_ERR_INVALID_ARGUMENT;
-    if (n < 0 || (n > 0 && (!points || !dist))) return fail(ctx, RM_ERR_INVALID_ARGUMENT, "rm_scene_eval: bad arguments");
+    if (n < 0 || (n > 0 && (!points || !dist)) || form < 0 || form >= rm::kFormCount)
+        return fail(ctx, RM_ERR_INVALID_ARGUMENT, std::string(what) + ": bad arguments");
     if (ctx->scene < 0) return fail(ctx, RM_ERR_NO_SCENE, "no scene loaded (rm_load_scene)");
+    const bool plugin = ctx->scene == rm::SCENE_PLUGIN;
+    if (plugin && form != RM_FORM_EXACT && !ctx->plugin.eval_probe)
+        return fail(ctx, RM_ERR_SCENE, std::string(what) + ": the scene plugin has no probe-form kernel "
+                                                           "(#define RM_PLUGIN_EVAL_PROBE in the scene source)");
     if (n == 0) return RM_OK;
     RM_HIP(hipSetDevice(ctx->device));
-    // device views of the three buffers (host ones are staged)
+    // device views of the four buffers (host ones are staged)
     const size_t pb = (size_t)n * 3 * sizeof(float), db = (size_t)n * sizeof(float), mb = (size_t)n * 16 * sizeof(float);
-    const bool dp = is_device_ptr(points), dd = is_device_ptr(dist), dm = !material || is_device_ptr(material);
+    const bool dp = is_device_ptr(points), dd = is_device_ptr(dist), dm = !material || is_device_ptr(material),
+               da = !aux || is_device_ptr(aux);
     char *tmp = nullptr;
-    if (!(dp && dd && dm)) RM_HIP(hipMalloc(&tmp, pb + db + (material ? mb : 0)));
+    if (!(dp && dd && dm && da)) RM_HIP(hipMalloc(&tmp, pb + db + (material ? mb : 0) + (aux ? db : 0)));
     const float *p = dp ? points : reinterpret_cast<float *>(tmp);
     float *d = dd ? dist : reinterpret_cast<float *>(tmp + pb);
     float *m = !material ? nullptr : dm ? material : reinterpret_cast<float *>(tmp + pb + db);
+    float *a = !aux ? nullptr : da ? aux : reinterpret_cast<float *>(tmp + pb + db + (material ? mb : 0));
     hipError_t e = hipSuccess;
     if (!dp) e = hipMemcpyAsync(const_cast<float *>(p), points, pb, hipMemcpyHostToDevice, ctx->stream);
     FrameConst F = frame_const(ctx, 1, 1, RowPart{1, 0, 1}, 1);
-    if (e == hipSuccess)
-        e = ctx->scene == rm::SCENE_PLUGIN ? rmplugin::launch_eval(ctx->plugin, F, ctx->uniform_values, p, n, d, m, ctx->stream)
-                                           : rm::launch_scene_eval(ctx->scene, F, p, n, d, m, ctx->stream);
+    auto probe = [&](int f, float *pd, float *pm) {
+        return plugin ? rmplugin::launch_eval_probe(ctx->plugin, F, ctx->uniform_values, p, n, pd, pm, a, ctx->stream)
+                      : rm::launch_scene_eval_form(ctx->scene, F, p, n, f, pd, pm, a, ctx->stream);
+    };
+    if (e == hipSuccess && form == RM_FORM_EXACT) {
+        e = plugin ? rmplugin::launch_eval(ctx->plugin, F, ctx->uniform_values, p, n, d, m, ctx->stream)
+                   : rm::launch_scene_eval(ctx->scene, F, p, n, d, m, ctx->stream);
+        if (e == hipSuccess && a)  // (a plugin's aux is 0)
+            e = plugin ? hipMemsetAsync(a, 0, db, ctx->stream) : probe(RM_FORM_PROBE, nullptr, nullptr);
+    } else if (e == hipSuccess) {
+        e = probe(form, d, m);
+    }
     if (e == hipSuccess && !dd) e = hipMemcpyAsync(dist, d, db, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess && material && !dm) e = hipMemcpyAsync(material, m, mb, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && aux && !da) e = hipMemcpyAsync(aux, a, db, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (tmp) (void)hipFree(tmp);
-    if (e != hipSuccess) return hip_fail(ctx, e, "rm_scene_eval");
+    if (e != hipSuccess) return hip_fail(ctx, e, what);
     return RM_OK;
+}
+
+rm_status rm_scene_eval(rm_ctx *ctx, const float *points, int64_t n, float *dist, float *material) {
+    return scene_eval_form(ctx, points, n, RM_FORM_EXACT, dist, material, nullptr, "rm_scene_eval");
+}
+
+static_assert(RM_FORM_EXACT == rm::kFormExact && RM_FORM_PROBE == rm::kFormProbe &&
+                  RM_FORM_PROBE_NB1 == rm::kFormProbeNb1,
+              "rm.h's rm_form are scene_eval_one's FORM");
+
+rm_status rm_scene_eval_form(rm_ctx *ctx, const float *points, int64_t n, int form, float *dist, float *material,
+                             float *aux) {
+    return scene_eval_form(ctx, points, n, form, dist, material, aux, "rm_scene_eval_form");
 }
 
 rm_status rm_compile_scene(const char *file_name, char *log, size_t log_size) {

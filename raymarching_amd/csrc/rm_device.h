@@ -157,6 +157,10 @@ struct ScenePolicy {
 // below): the exact form keeps the GLSL's roundings, the probe form serves the
 // AO / shadow / thickness probes, whose results are smooth in the distance.
 constexpr bool kExactForm = true, kProbeForm = false;
+// The forms rm_scene_eval_form evaluates at caller-supplied points (rm.h's
+// rm_form): the exact form; the probe form; the probe form with one fold exit
+// test (sponge_folds' NB = 1: scene T's latency tiles; the probe form elsewhere)
+constexpr int kFormExact = 0, kFormProbe = 1, kFormProbeNb1 = 2, kFormCount = 3;
 
 // ------------------------------------------------------------- vec3 helpers
 struct V3 {

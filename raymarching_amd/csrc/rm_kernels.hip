@@ -291,6 +291,25 @@ hipError_t launch_scene_eval(int scene, const FrameConst& F, const float* pts, l
     }
 }
 
+#define RM_EVAL_FORM_LAUNCHER(name)                                                                       \
+    hipError_t name(const FrameConst& F, const float* pts, long long n, int form, float* dist, float* mat, \
+                    float* aux, hipStream_t s);
+RM_EVAL_FORM_LAUNCHER(launch_eval_form_s0)
+RM_EVAL_FORM_LAUNCHER(launch_eval_form_t)
+RM_EVAL_FORM_LAUNCHER(launch_eval_form_o)
+RM_EVAL_FORM_LAUNCHER(launch_eval_form_og)
+
+hipError_t launch_scene_eval_form(int scene, const FrameConst& F, const float* pts, long long n, int form, float* dist,
+                                  float* mat, float* aux, hipStream_t s) {
+    switch (scene) {
+    case SCENE_S0: return launch_eval_form_s0(F, pts, n, form, dist, mat, aux, s);
+    case SCENE_T: return launch_eval_form_t(F, pts, n, form, dist, mat, aux, s);
+    case SCENE_O: return launch_eval_form_o(F, pts, n, form, dist, mat, aux, s);
+    case SCENE_OG: return launch_eval_form_og(F, pts, n, form, dist, mat, aux, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
 template <typename E>
 static hipError_t deinterleave_t(const E* gathered, E* out, int W, int H, int band, int nshards, int rows_per_shard,
                                  hipStream_t s) {

@@ -38,6 +38,33 @@ hipError_t launch_eval(const FrameConst& F, const float* pts, long long n, float
     return hipGetLastError();
 }
 
+// rm_scene_eval_form's probe forms (scene_eval_one's FORM): kernels of their
+// own, so that rm_scene_eval's keeps its code
+template <int SC, int FORM>
+__global__ __launch_bounds__(256) void rm_scene_eval_form(FrameConst F, const float* __restrict__ pts, long long n,
+                                                          float* __restrict__ dist, float* __restrict__ mat,
+                                                          float* __restrict__ aux) {
+    scene_eval_one<SC, FORM>(F, pts, n, dist, mat, aux);
+}
+
+// form: kFormProbe or kFormProbeNb1 (the same kernel but for scene T); dist,
+// mat and aux may each be null
+template <int SC>
+hipError_t launch_eval_form(const FrameConst& F, const float* pts, long long n, int form, float* dist, float* mat,
+                            float* aux, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    if (form != kFormProbe && form != kFormProbeNb1) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if constexpr (SC == SCENE_T) {
+        if (form == kFormProbeNb1) {
+            hipLaunchKernelGGL((rm_scene_eval_form<SC, kFormProbeNb1>), grid, block, 0, s, F, pts, n, dist, mat, aux);
+            return hipGetLastError();
+        }
+    }
+    hipLaunchKernelGGL((rm_scene_eval_form<SC, kFormProbe>), grid, block, 0, s, F, pts, n, dist, mat, aux);
+    return hipGetLastError();
+}
+
 template <int SC, int K, typename OUT>
 hipError_t launch_direct(const FrameConst& F, OUT* out, unsigned long long* evals, hipStream_t s) {
     using T = Tiling<K>;

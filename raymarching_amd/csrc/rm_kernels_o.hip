@@ -27,6 +27,15 @@ hipError_t launch_eval_og(const FrameConst& F, const float* pts, long long n, fl
     return launch_eval<SCENE_OG>(F, pts, n, dist, mat, s);
 }
 
+hipError_t launch_eval_form_o(const FrameConst& F, const float* pts, long long n, int form, float* dist,
+                              float* mat, float* aux, hipStream_t s) {
+    return launch_eval_form<SCENE_O>(F, pts, n, form, dist, mat, aux, s);
+}
+hipError_t launch_eval_form_og(const FrameConst& F, const float* pts, long long n, int form, float* dist,
+                               float* mat, float* aux, hipStream_t s) {
+    return launch_eval_form<SCENE_OG>(F, pts, n, form, dist, mat, aux, s);
+}
+
 hipError_t launch_wire_o(const FrameConst& F, WireTile* slots, unsigned long long* evals, hipStream_t s) {
     return launch_scene_wire<SCENE_O>(F, slots, evals, s);
 }

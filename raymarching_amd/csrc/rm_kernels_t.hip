@@ -21,6 +21,15 @@ hipError_t launch_eval_t(const FrameConst& F, const float* pts, long long n, flo
     return launch_eval<SCENE_T>(F, pts, n, dist, mat, s);
 }
 
+hipError_t launch_eval_form_s0(const FrameConst& F, const float* pts, long long n, int form, float* dist,
+                               float* mat, float* aux, hipStream_t s) {
+    return launch_eval_form<SCENE_S0>(F, pts, n, form, dist, mat, aux, s);
+}
+hipError_t launch_eval_form_t(const FrameConst& F, const float* pts, long long n, int form, float* dist,
+                              float* mat, float* aux, hipStream_t s) {
+    return launch_eval_form<SCENE_T>(F, pts, n, form, dist, mat, aux, s);
+}
+
 hipError_t launch_wire_s0(const FrameConst& F, WireTile* slots, unsigned long long* evals, hipStream_t s) {
     return launch_scene_wire<SCENE_S0>(F, slots, evals, s);
 }

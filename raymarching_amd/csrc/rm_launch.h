@@ -30,6 +30,10 @@ hipError_t launch_render(int scene, const FrameConst& F, void* out, bool rgba8, 
 // sceneSDF(p) of a compiled-in scene at n points (rm_scene_eval)
 hipError_t launch_scene_eval(int scene, const FrameConst& F, const float* pts, long long n, float* dist, float* mat,
                              hipStream_t s);
+// its probe forms (rm_scene_eval_form: form = kFormProbe or kFormProbeNb1);
+// dist, mat and aux (scene O's probe-form slack, 0 elsewhere) may each be null
+hipError_t launch_scene_eval_form(int scene, const FrameConst& F, const float* pts, long long n, int form, float* dist,
+                                  float* mat, float* aux, hipStream_t s);
 hipError_t launch_deinterleave(const float4* gathered, float4* out, int W, int H, int band, int nshards,
                                int rows_per_shard, hipStream_t s);
 hipError_t launch_deinterleave_u32(const uint32_t* gathered, uint32_t* out, int W, int H, int band, int nshards,

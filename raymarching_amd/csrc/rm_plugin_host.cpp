@@ -220,8 +220,7 @@ std::string translation_unit(const std::string& src, const std::string& file, co
            instance("namespace rm {\nnamespace glsl {\n", "}  // namespace glsl\n}  // namespace rm\n", "", "") +
            instance("namespace rm {\nnamespace glsl {\nnamespace probe {\n",
                     "}  // namespace probe\n}  // namespace glsl\n}  // namespace rm\n",
-                    "#pragma clang fp contract(fast)\n#if RM_PROBE_REASSOC\n#pragma clang fp reassociate(on)\n#endif\n",
-                    "#if RM_PROBE_REASSOC\n#pragma clang fp reassociate(off)\n#endif\n#pragma clang fp contract(off)\n") +
+                    "#pragma clang fp contract(fast)\n", "#pragma clang fp contract(off)\n") +
            undefs + "#include \"rm_plugin_kernels.h\"\n";
 }
 
@@ -300,6 +299,10 @@ hipError_t load(const Code& code, int uniform_slots, Module& m) {
         (void)hipModuleUnload(n.mod);
         return e;
     }
+    if (hipModuleGetFunction(&n.eval_probe, n.mod, "rm_plugin_eval_probe") != hipSuccess) {
+        (void)hipGetLastError();  // a scene without RM_PLUGIN_EVAL_PROBE
+        n.eval_probe = nullptr;
+    }
     n.code = code;
     n.uniform_slots = uniform_slots;
     unload(m);
@@ -341,6 +344,23 @@ hipError_t launch_eval(const Module& m, const rm::FrameConst& F, const uint32_t*
     void* with_block[] = {&f, const_cast<uint32_t*>(uniforms), &p, &nn, &d, &mm};
     void* args[] = {&f, &p, &nn, &d, &mm};
     return hipModuleLaunchKernel(m.eval, (unsigned)((n + 255) / 256), 1, 1, 256, 1, 1, 0, s,
+                                 m.uniform_slots > 0 ? with_block : args, nullptr);
+}
+
+hipError_t launch_eval_probe(const Module& m, const rm::FrameConst& F, const uint32_t* uniforms, const float* pts,
+                             long long n, float* dist, float* mat, float* aux, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    if (!m.eval_probe) return hipErrorInvalidDeviceFunction;
+    rm::FrameConst f = F;
+    const float* p = pts;
+    long long nn = n;
+    float* d = dist;
+    float* mm = mat;
+    float* a = aux;
+    // (the uniform block is read now, as launch_eval's)
+    void* with_block[] = {&f, const_cast<uint32_t*>(uniforms), &p, &nn, &d, &mm, &a};
+    void* args[] = {&f, &p, &nn, &d, &mm, &a};
+    return hipModuleLaunchKernel(m.eval_probe, (unsigned)((n + 255) / 256), 1, 1, 256, 1, 1, 0, s,
                                  m.uniform_slots > 0 ? with_block : args, nullptr);
 }
 

@@ -39,6 +39,7 @@ struct Module {
     hipFunction_t render = nullptr;        // timed render kernel; null for an RM_PLUGIN_EVAL_ONLY scene
     hipFunction_t render_count = nullptr;  // instrumented render kernel (ray-step counts, step maps)
     hipFunction_t eval = nullptr;
+    hipFunction_t eval_probe = nullptr;    // rm_scene_eval_form's probe forms; null unless the scene defines RM_PLUGIN_EVAL_PROBE
     hipFunction_t cast = nullptr;          // rm_cast_rays' march (RM_PLUGIN_EVAL_ONLY scenes have it too)
     hipFunction_t shade = nullptr;         // rm_shade_rays' kernel; null for an RM_PLUGIN_EVAL_ONLY scene
     Code code;
@@ -53,6 +54,10 @@ hipError_t launch_render(const Module& m, const rm::FrameConst& F, const uint32_
                          unsigned long long* evals, hipStream_t s);
 hipError_t launch_eval(const Module& m, const rm::FrameConst& F, const uint32_t* uniforms, const float* pts,
                        long long n, float* dist, float* mat, hipStream_t s);
+// the probe instance's distance and material (dist, mat and aux may each be null; aux receives 0);
+// hipErrorInvalidDeviceFunction for a scene that does not define RM_PLUGIN_EVAL_PROBE
+hipError_t launch_eval_probe(const Module& m, const rm::FrameConst& F, const uint32_t* uniforms, const float* pts,
+                             long long n, float* dist, float* mat, float* aux, hipStream_t s);
 // `block`: threads per workgroup (rm::cast_block_size)
 hipError_t launch_cast(const Module& m, const rm::FrameConst& F, const uint32_t* uniforms, const rm::RayQuery& Q,
                        int inside, int block, hipStream_t s);

@@ -27,6 +27,8 @@ struct rm::PluginScene<rm::SCENE_PLUGIN> {
     // the probe form: the scene compiled against the library's probe instance
     __device__ __forceinline__ static float dist_probe(rm::V3 p) { return rm::glsl::probe::sceneSDF(p).dist; }
     __device__ __forceinline__ static rm::Mat mat(rm::V3 p) { return rm::glsl::sceneSDF(p).mat; }
+    // the probe instance's material: rm_plugin_eval_probe alone reads it (renders shade with mat)
+    __device__ __forceinline__ static rm::Mat mat_probe(rm::V3 p) { return rm::glsl::probe::sceneSDF(p).mat; }
 };
 
 #ifndef RM_PLUGIN_EVAL_ONLY
@@ -95,6 +97,20 @@ extern "C" __global__ __launch_bounds__(256) void rm_plugin_eval(rm::FrameConst 
     RM_UNIFORM_PRELOAD();
     rm::scene_eval_one<rm::SCENE_PLUGIN>(F, pts, n, dist, mat);
 }
+
+// the probe instance's sceneSDF(p) at explicit points (rm_scene_eval_form's
+// probe forms: distance and material of rm::glsl::probe; aux receives 0).
+// Only for a scene that defines RM_PLUGIN_EVAL_PROBE: one more copy of the
+// scene to compile (the plugin section's compile times), which
+// tests and tools ask for and a scene that is only rendered does not need.
+#ifdef RM_PLUGIN_EVAL_PROBE
+extern "C" __global__ __launch_bounds__(256) void rm_plugin_eval_probe(rm::FrameConst F,
+                                                                       RM_UNIFORM_PARAM const float* pts, long long n,
+                                                                       float* dist, float* mat, float* aux) {
+    RM_UNIFORM_PRELOAD();
+    rm::scene_eval_one<rm::SCENE_PLUGIN, rm::kFormProbe>(F, pts, n, dist, mat, aux);
+}
+#endif
 
 // castRayD / castRayDI over caller-supplied rays (rm_cast_rays, rm_rays.h)
 extern "C" __global__ __launch_bounds__(256) void rm_plugin_cast(rm::FrameConst F, RM_UNIFORM_PARAM rm::RayQuery Q,

@@ -836,16 +836,34 @@ __device__ __forceinline__ V3 render_pixel(const FrameConst& F, V3 ro, V3 rd, Ta
 // sceneSDF(p) of the scene at n points (rm_scene_eval): the distance in the
 // reference's arithmetic (the EXACT form), and, when mat is set, the 16 floats
 // of struct Material (common.frag:20-35) in declaration order.
-template <int SC>
+//
+// FORM (rm_scene_eval_form): kFormExact is the above.  kFormProbe /
+// kFormProbeNb1 store scene_dist<SC, kProbeForm> (NB = 3 / 1) instead, where
+// dist is set, and into aux, where it is set, the probe form's slack of
+// scene_dist_O (the value plane_probes thresholds; 0 for the other scenes).
+// The material is scene_mat's in every form, except a plugin's, which comes
+// from the instance of the scene library the distance came from.
+template <int SC, int FORM = kFormExact>
 __device__ __forceinline__ void scene_eval_one(const FrameConst& F, const float* pts, long long n, float* dist,
-                                               float* mat) {
+                                               float* mat, float* aux = nullptr) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const V3 p = v3(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]);
     Tally t;
-    dist[i] = scene_dist<SC, kExactForm>(F, p, t);
+    if constexpr (FORM == kFormExact) {
+        dist[i] = scene_dist<SC, kExactForm>(F, p, t);
+    } else {
+        float d, slack = 0.0f;
+        // scene O: scene_dist's own call, with its slack (one evaluation gives both)
+        if constexpr (SC == SCENE_O || SC == SCENE_OG) d = scene_dist_O<kProbeForm>(p, sponge_space<kProbeForm>(F, p), t, slack);
+        else d = scene_dist<SC, kProbeForm, FORM == kFormProbeNb1 ? 1 : 3>(F, p, t);
+        if (dist) dist[i] = d;
+        if (aux) aux[i] = slack;
+    }
     if (mat) {
-        const Mat m = scene_mat<SC>(F, p);
+        Mat m;
+        if constexpr (SC == SCENE_PLUGIN && FORM != kFormExact) m = PluginScene<SC>::mat_probe(p);
+        else m = scene_mat<SC>(F, p);
         const float v[16] = {m.diffuse.x,    m.diffuse.y,    m.diffuse.z,    m.specular.x,    m.specular.y,  m.specular.z,
                              m.shininess,    m.reflectivity, m.transparency, m.absorption.x,  m.absorption.y,
                              m.absorption.z, m.refraction_index,          m.emission.x,   m.emission.y,    m.emission.z};

@@ -111,5 +111,7 @@ def kat_function() -> str:
 def plugin_source() -> str:
     """The cases as a scene plugin: sceneSDF(p) = case int(u_time) at p."""
     return ("// generated by tests/golden/lib_kat_cases.py (scene-library known answers)\n"
-            "#define RM_PLUGIN_EVAL_ONLY\n" + PRELUDE + kat_function() +
+            "#define RM_PLUGIN_EVAL_ONLY\n"
+            "#define RM_PLUGIN_EVAL_PROBE  // rm_scene_eval_form's probe forms (rm_plugin_kernels.h)\n" +
+            PRELUDE + kat_function() +
             "SdResult sceneSDF(vec3 p)\n{\n\treturn kat(int(u_time), p);\n}\n")

@@ -16,6 +16,8 @@ import numpy as np
 import pytest
 
 import raymarching_amd as rm
+from tests import lib_edges as edges
+from tests import lib_ref64 as ref64
 from tests.golden import lib_kat_cases as kat
 from tests.parity import assert_parity
 
@@ -43,6 +45,21 @@ def kat_file(tmp_path_factory):
 @pytest.mark.parametrize("name", sorted(SCENES))
 def test_example_scene_compiles(name):
     ok, log = rm.compile_scene(scene_path(name))
+    assert ok, log
+
+
+def probe_wrapper(tmp_path, name):
+    """An example scene with the kernel of rm_scene_eval_form's probe forms,
+    which a scene asks for by defining RM_PLUGIN_EVAL_PROBE (rm_plugin_kernels.h:
+    one more copy of the scene to compile, so the examples do not)."""
+    p = tmp_path / f"probe_{SCENES[name]}"
+    p.write_text(f'#define RM_PLUGIN_EVAL_PROBE\n#include "{scene_path(name)}"\n')
+    return str(p)
+
+
+@pytest.mark.parametrize("name", sorted(SCENES))
+def test_example_scene_compiles_with_the_probe_eval_kernel(name, tmp_path):
+    ok, log = rm.compile_scene(probe_wrapper(tmp_path, name))
     assert ok, log
 
 
@@ -149,6 +166,131 @@ def test_scene_library_known_answers(R, kat_file):
             bad.append(f"{name}: {int((~ok).sum())} points off, e.g. p={pts[j]} dist {dist[j]} vs "
                        f"{z['dist'][i][j]}, mat {mat[j][:4]} vs {z['mat'][i][j][:4]}")
     assert not bad, "\n".join(bad)
+
+
+@pytest.mark.gpu
+def test_scene_library_probe_instance_known_answers(R, kat_file):
+    """The same cases through the library's second instance (rm::glsl::probe,
+    rm_sdf_lib_body.h with RM_LIB_PROBE 1: FMA contraction, hardware exp2 / log2
+    / rcp, the rint folds, identity rotations dropped), which AO, soft shadows
+    and thickness probes run and no other test evaluates at a point:
+    rm_scene_eval_form's RM_FORM_PROBE, distance and material both from the
+    probe instance, against the SwiftShader answers under the case's class
+    tolerance and the class's allowed point count (no case needed a bound of
+    its own; measured on the MI355X: the exact-class cases within 4.8e-7 on the
+    distance and 2.3e-5 on a blended material, the trans class within 4.8e-7,
+    mandelbulb's distance within 9.5e-6 and log(m) within 0.0183 of ~20).
+    Prints per case the share of bit-exact points and the maximum deviations."""
+    z = np.load(os.path.join(GOLDEN, "LIB_kat.npz"), allow_pickle=False)
+    pts = z["points"]
+    R.load_scene(kat_file)
+    bad = []
+    for i, (name, _, cls) in enumerate(kat.CASES):
+        R.set_uniform("u_time", float(i))
+        dist, mat, aux = R.scene_eval(pts, material=True, form="probe", aux=True)
+        assert not aux.any()  # (scene O's; 0 for a plugin)
+        assert np.array_equal(R.scene_eval(pts, form="probe_nb1"), dist)  # an alias for plugins
+        rel, ab, allowed = kat.TOL[cls]
+        exact = float(np.mean((dist == z["dist"][i]) & (mat == z["mat"][i]).all(-1)))
+        print(f"LIB_kat probe {name} [{cls}]: {exact:.3f} of points bit-exact, max |d dist| "
+              f"{float(np.max(np.abs(dist.astype(np.float64) - z['dist'][i]))):.3g}, max |d mat| "
+              f"{float(np.max(np.abs(mat.astype(np.float64) - z['mat'][i]))):.3g}")
+        ok = _within(dist, z["dist"][i], rel, ab)
+        mat_ok = _within(mat, z["mat"][i], rel, ab)
+        if name == "mengersponge":
+            # which fold won (res.y, res.z: diffuse.y, diffuse.z) is decided by the
+            # last bit where a fold's c ties the d before it, on whole regions of
+            # the sponge (tests/lib_ref64.py): there those two floats are not compared
+            res = ref64.evaluate(name, pts)
+            und, tie = ref64.undecided(res, rel, ab)
+            print(f"LIB_kat probe {name}: {int(und.sum())} undecided points ({int(tie.sum())} exact ties), which "
+                  f"fold won differs at {int((~mat_ok.all(-1)).sum())} ({int((~mat_ok.all(-1) & ~und).sum())} decided)")
+            mat_ok |= und[:, None] & res.disc[None, 1:]
+        mat_ok = mat_ok.all(-1)
+        ok &= mat_ok
+        if int((~ok).sum()) > allowed:
+            j = int(np.argmin(ok))
+            bad.append(f"{name}: {int((~ok).sum())} points off, e.g. p={pts[j]} dist {dist[j]} vs "
+                       f"{z['dist'][i][j]}, mat {mat[j][:4]} vs {z['mat'][i][j][:4]}")
+    assert not bad, "\n".join(bad)
+
+
+@pytest.fixture(scope="module")
+def edge_file(tmp_path_factory):
+    p = tmp_path_factory.mktemp("kat") / "lib_edges.hip"
+    p.write_text(ref64.plugin_source2())
+    return str(p)
+
+
+def test_edge_set_plugin_compiles(edge_file):
+    ok, log = rm.compile_scene(edge_file)
+    assert ok, log
+
+
+@pytest.mark.gpu
+def test_scene_library_at_its_edges_against_float64(R, edge_file):
+    """Both instances of the library, exact and probe, at the edge sets of
+    tests/lib_edges.py (adjacent floats around every branch of a case, negative
+    and far coordinates, box faces, the angle set of the rotations, the literal
+    angle 0 the probe instance drops) against the float64 restatement
+    tests/lib_ref64.py under the case's class tolerance: no point allowed
+    outside it; at undecided points the continuous outputs only.  Prints per
+    case and instance the share of points equal to the rounded reference and
+    the largest deviation.
+    Measured on the MI355X, largest deviation of a compared output per class,
+    both instances alike: exact 2.2e-5 (on a blended shininess of ~50; 5e-7 on
+    distances), trans 3.0e-6, fractal 1.0e-3; no point outside its bound."""
+    runs = [(i, name, cls, None) for i, (name, _, cls) in enumerate(kat.CASES)]
+    for k, (name, _, cls, angle) in enumerate(ref64.cases2()):
+        runs += [(len(kat.CASES) + k, name, cls, a) for a in (ref64.ANGLES if angle is None else (angle,))]
+    R.load_scene(edge_file)
+    bad, worst = [], {}
+    for i, name, cls, angle in runs:
+        R.set_uniform("u_time", float(i))
+        R.set_uniform("u_mouse", 0.0 if angle is None else float(angle), 0.0)
+        pts = edges.edge_points(name)
+        res = ref64.evaluate(name, pts, angle)
+        rel, ab, _ = kat.TOL[cls]
+        for form in ("exact", "probe"):
+            dist, mat = R.scene_eval(pts, material=True, form=form)
+            ok, dev = ref64.compare(res, dist, mat, rel, ab)
+            same = float(np.mean((dist == res.out[:, 0].astype(np.float32)) &
+                                 (mat == res.out[:, 1:].astype(np.float32)).all(-1)))
+            tag = name if angle is None else f"{name} angle {angle:g}"
+            print(f"LIB edges {tag} [{cls}] {form}: {len(pts)} points, {same:.3f} equal to the rounded reference, "
+                  f"max deviation {dev:.3g}, {int((~ok).sum())} outside")
+            worst[(cls, form)] = max(worst.get((cls, form), 0.0), dev)
+            if not ok.all():
+                j = int(np.argmin(ok))
+                bad.append(f"{tag} {form}: {int((~ok).sum())} of {len(pts)} points off, e.g. p={pts[j].tolist()} dist "
+                           f"{dist[j]!r} vs {res.out[j, 0]!r}, diffuse {mat[j][:3]} vs {res.out[j, 1:4]}")
+    print("LIB edges worst deviation per class and instance:", {f"{k[0]}/{k[1]}": f"{v:.3g}" for k, v in worst.items()})
+    assert not bad, "\n".join(bad)
+
+
+@pytest.mark.gpu
+def test_output_shader_plugin_probe_instance_matches_oracle(R, tmp_path):
+    """scenes/output_shader.hip over the probe instance (transformR,
+    mengersponge's rint branch, sminCubic through div_k's reciprocal) against
+    the oracle's scene O: every point within 1e-5 + 1e-5 |d|, the built-in probe
+    form's bound (tests/test_probe_forms.py), no allowance.  A scene without
+    RM_PLUGIN_EVAL_PROBE has no such kernel and says so."""
+    import oracle
+    rng = np.random.default_rng(7)
+    pts = rng.uniform([-8, -1, -8], [8, 7, 8], (4096, 3)).astype(np.float32)
+    R.load_scene(probe_wrapper(tmp_path, "O"))
+    R.set_uniform("u_time", 3.5)
+    d = R.scene_eval(pts, form="probe")
+    o = oracle.scene_dist("O", pts, time=3.5)
+    err = np.abs(d.astype(np.float64) - o)
+    print(f"plugin O probe instance vs oracle: max |d| {err.max():.3g} at p={pts[np.argmax(err)].tolist()}, "
+          f"{float(np.mean(d == o)):.3f} bit-exact")
+    assert _within(d, o, 1e-5, 1e-5).all(), (int((~_within(d, o, 1e-5, 1e-5)).sum()), float(err.max()))
+    R.load_scene(scene_path("O"))
+    with pytest.raises(rm.RmError, match="RM_PLUGIN_EVAL_PROBE"):
+        R.scene_eval(pts[:4], form="probe")
+    d0, a0 = R.scene_eval(pts[:4], aux=True)  # the exact form needs no such kernel
+    assert np.isfinite(d0).all() and not a0.any()
 
 
 @pytest.mark.gpu
