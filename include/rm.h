@@ -556,6 +556,15 @@ rm_status rm_post_frag(rm_ctx *ctx, int W, int H, int sample, int tonemap, const
 rm_status rm_post_chain_ex(rm_ctx *ctx, int W, int H, int sample, int tonemap, const uint32_t *in, uint32_t *mid,
                            uint32_t *out);
 
+/* Scenes S0/T keep the device's reciprocals of the frame size and of
+ * u_resolution.y per resolution (W, H, u_resolution.y) in a small cache of the
+ * context: the first render of a new resolution runs a one-thread kernel on the
+ * context's stream and waits for it (so it must not fall inside a stream
+ * capture); later frames of that resolution, whatever their pose and time, do
+ * not.  entries: resolutions held now; capacity: the most it holds (the least
+ * recently used one is replaced).  Either pointer may be NULL. */
+rm_status rm_resolution_cache_info(rm_ctx *ctx, int *entries, int *capacity);
+
 /* The render kernels' code objects by content (16 hex digits of a SHA-256 of
  * the translation units that hold them): rocprofv3 counters of a render launch
  * (profiles/pmc_counters.json) name the build they counted, and bench.py

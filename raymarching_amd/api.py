@@ -177,6 +177,13 @@ class Renderer:
     def synchronize(self) -> None:
         check(lib().rm_synchronize(self._ctx), self._ctx)
 
+    def resolution_cache(self) -> tuple:
+        """rm_resolution_cache_info: (entries, capacity) of the context's
+        per-resolution cache of scenes S0/T's camera reciprocals."""
+        n, cap = ctypes.c_int(), ctypes.c_int()
+        check(lib().rm_resolution_cache_info(self._ctx, ctypes.byref(n), ctypes.byref(cap)), self._ctx)
+        return n.value, cap.value
+
     # --- passes ----------------------------------------------------------
     @staticmethod
     def _ptr(t):

@@ -38,7 +38,8 @@ rm_status refine_dev(rm_ctx *ctx, int W, int H, const rm_aa_params &p, uint32_t 
     uint32_t *count = ctx->aa_queue, *queue = ctx->aa_queue + rm::kAaHeadWords;
     RowPart part;
     (void)rm::band_part(H, 1, 0, part);  // the whole frame, as rm_render_rgba8's launch
-    const FrameConst F = frame_const(ctx, W, H, part, H);
+    FrameConst F = frame_const(ctx, W, H, part, H);
+    if (rm_status st = frame_rcp(ctx, F)) return st;
     if (stats && !ctx->aa_ev2) RM_HIP(hipEventCreate(&ctx->aa_ev2));
     RM_HIP(hipMemsetAsync(count, 0, sizeof(uint32_t), ctx->stream));
     if (stats) RM_HIP(hipEventRecord(ctx->ev0, ctx->stream));

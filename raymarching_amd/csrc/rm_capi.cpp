@@ -93,6 +93,7 @@ rm_status rm_destroy(rm_ctx *ctx) {
     wait_idle(ctx);
     rmplugin::unload(ctx->plugin);
     if (ctx->d_evals) (void)hipFree(ctx->d_evals);
+    if (ctx->d_rcp) (void)hipFree(ctx->d_rcp);
     for (auto &b : ctx->persist) {
         if (b.ctr) (void)hipFree(b.ctr);
         if (b.last) (void)hipEventDestroy(b.last);
@@ -844,6 +845,13 @@ rm_status rm_compile_scene(const char *file_name, char *log, size_t log_size) {
 }
 
 int rm_abi_version(void) { return RM_ABI_VERSION; }
+
+rm_status rm_resolution_cache_info(rm_ctx *ctx, int *entries, int *capacity) {
+    if (!ctx) return RM_ERR_INVALID_ARGUMENT;
+    if (entries) *entries = ctx->rcp_n;
+    if (capacity) *capacity = rm_ctx::kRcpEntries;
+    return RM_OK;
+}
 
 const char *rm_last_error(rm_ctx *ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 

@@ -83,6 +83,22 @@ struct rm_ctx {
     hipStream_t aa_stream = nullptr;
     bool aa_pending = false;
     hipEvent_t aa_ev2 = nullptr;  // a third timing event (rm_aa_stats: detect | refine), made on first use
+    // FrameConst.rcp_* of scenes S0/T (rm_render_host.cpp frame_rcp): the device's reciprocals of the frame
+    // size and of u_resolution.y, kept per resolution -- the key changes when a window is resized, not per frame
+    // (u_time and the pose do not enter it).  A small fixed-size cache, least recently used out, so that callers
+    // alternating between a few sizes do not synchronise on every call; a miss runs a one-thread kernel on the
+    // context's stream and waits for it.  Per context, so per GPU.
+    struct RcpEntry {
+        int W = 0, H = 0;
+        uint32_t res_y_bits = 0;
+        float rcp[3] = {0.0f, 0.0f, 0.0f};
+        uint64_t used = 0;
+    };
+    static constexpr int kRcpEntries = 8;
+    RcpEntry rcp_cache[kRcpEntries];
+    int rcp_n = 0;
+    uint64_t rcp_clock = 0;
+    float *d_rcp = nullptr;   // the kernel's three floats (made on the first miss)
     rmplugin::Module plugin;  // the loaded scene plugin (scene == SCENE_PLUGIN)
     // the uniforms the loaded scene declares itself (empty for a built-in
     // scene) and their current values, the block every plugin launch passes by
@@ -177,6 +193,9 @@ void wait_idle(rm_ctx *ctx);                       // rm_destroy: nothing the co
 // ---- rm_render_host.cpp
 int pick_kernel(const rm_params &p);
 rm::FrameConst frame_const(const rm_ctx *c, int W, int H, const rm::RowPart &part, int nrows);
+// F.rcp_* for F's W, H and res_y (scenes S0/T; every launch whose kernel builds camera rays calls it after
+// frame_const, which leaves them 0): from the context's per-resolution cache, computed on the device on a miss
+rm_status frame_rcp(rm_ctx *ctx, rm::FrameConst &F);
 // rm_render_cycle_rows_wire: the compressed wire's message instead of pixels
 // (`out` is then the tile-slot workspace, rm_wire_tile.h)
 struct WireOut {

@@ -73,6 +73,14 @@ struct FrameConst {
     int far_sky;                   // scene T with max_steps >= rmfs::kFarSkyN0: waves whose rays all pass
                                    // rmfs::far_sky_ray skip the primary and the reflection march (rm_far_sky.h;
                                    // in the struct's tail padding: no other member moves)
+    // (the members below are new at the struct's end: nothing before them moves)
+    float rcp_w, rcp_h, rcp_res_y;  // scenes S0/T (camera_ray<FAST>): v_rcp_f32 of (float)W, (float)H and res_y,
+                                    // computed on the device once per resolution (rm_render_host.cpp frame_rcp;
+                                    // the host cannot restate v_rcp_f32) instead of per wave
+    int tile_run;                   // scenes S0/T, rm_rows.h wave_row_mode: 1 the part is the whole frame (y = j);
+                                    // 2 every wave's rows lie in one run (render_tile_at finds the run once per
+                                    // wave, shard_row_of_wave); 0 (a band of 3, ragged parts, a part starting
+                                    // inside a wave's rows): each lane divides
 };
 static_assert(rmfs::kFarSkyDepth == ZFAR, "rm_far_sky.h restates ZFAR");
 
@@ -144,6 +152,9 @@ struct ScenePolicy {
     static constexpr bool kPlaneSpans = SC == SCENE_O || SC == SCENE_OG;
     static constexpr bool kProbeFma = kPlaneSpans;
     static constexpr bool kSettleO = kPlaneSpans;
+    // Scenes S0/T: a wave's frame rows from one scalar division per wave where the layout allows
+    // (shard_row_of_wave, rm_render_direct.h; FrameConst.tile_run)
+    static constexpr bool kTileRow = kHwMath;
     // Scene T: the far-sky shortcut of render_T_from (rm_far_sky.h)
     static constexpr bool kFarSky = SC == SCENE_T;
     // Minimum waves per SIMD the register allocator must allow.  Scene O asks

@@ -30,6 +30,19 @@ hipError_t launch_eval_form_t(const FrameConst& F, const float* pts, long long n
     return launch_eval_form<SCENE_T>(F, pts, n, form, dist, mat, aux, s);
 }
 
+// FrameConst.rcp_*: v_rcp_f32 of the frame size and of u_resolution.y, the floats camera_ray<FAST> divided by in
+// every wave before they were members (one thread; the host keeps them per resolution, rm_render_host.cpp frame_rcp)
+__global__ __launch_bounds__(64) void rm_resolution_rcp(int W, int H, float res_y, float* __restrict__ out3) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    out3[0] = __builtin_amdgcn_rcpf((float)W);
+    out3[1] = __builtin_amdgcn_rcpf((float)H);
+    out3[2] = __builtin_amdgcn_rcpf(res_y);
+}
+hipError_t launch_resolution_rcp(int W, int H, float res_y, float* out3, hipStream_t s) {
+    hipLaunchKernelGGL(rm_resolution_rcp, dim3(1), dim3(64), 0, s, W, H, res_y, out3);
+    return hipGetLastError();
+}
+
 hipError_t launch_wire_s0(const FrameConst& F, WireTile* slots, unsigned long long* evals, hipStream_t s) {
     return launch_scene_wire<SCENE_S0>(F, slots, evals, s);
 }

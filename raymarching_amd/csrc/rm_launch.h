@@ -27,6 +27,8 @@ hipError_t launch_render_wire(int scene, const FrameConst& F, WireTile* slots, u
                               hipStream_t s);
 hipError_t launch_render(int scene, const FrameConst& F, void* out, bool rgba8, unsigned long long* evals, int kernel,
                          hipStream_t s);
+// scenes S0/T: out3 (device) = v_rcp_f32 of (float)W, (float)H, res_y (FrameConst.rcp_*; rm_kernels_t.hip)
+hipError_t launch_resolution_rcp(int W, int H, float res_y, float* out3, hipStream_t s);
 // sceneSDF(p) of a compiled-in scene at n points (rm_scene_eval)
 hipError_t launch_scene_eval(int scene, const FrameConst& F, const float* pts, long long n, float* dist, float* mat,
                              hipStream_t s);

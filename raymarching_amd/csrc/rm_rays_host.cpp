@@ -140,7 +140,8 @@ rm_status rm_camera_rays(rm_ctx *ctx, int W, int H, float *origin3, float *direc
     rm::TraceRange range("rm_camera_rays");
     const bool dev_o = is_device_ptr(origin3), dev_d = is_device_ptr(directions);
     const size_t bytes = (size_t)W * H * 3 * sizeof(float);
-    const FrameConst F = frame_const(ctx, W, H, RowPart{1, 0, 1}, H);
+    FrameConst F = frame_const(ctx, W, H, RowPart{1, 0, 1}, H);
+    if (rm_status st = frame_rcp(ctx, F)) return st;
     // the form of the loaded scene's render kernel (a plugin's: output_shader.frag's pass)
     const bool fast = ctx->scene == rm::SCENE_S0   ? rm::ScenePolicy<rm::SCENE_S0>::kHwMath
                       : ctx->scene == rm::SCENE_T  ? rm::ScenePolicy<rm::SCENE_T>::kHwMath

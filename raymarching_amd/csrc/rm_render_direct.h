@@ -64,14 +64,26 @@ __device__ __forceinline__ float dist_at(const FrameConst& F, V3 p, Tally& cnt, 
     else return dist_probe<SC, NB>(F, p, cnt);
 }
 
+// Scene T's probes in a far-sky wave of the timed kernels (render_T_from, rm_far_sky.h): every
+// lane's far point has max|q| >= kFarSkyFar = 4.1; the normal's probes lie 0.0018 from it and the AO probes at most
+// 0.81 (4 * 0.2 |n|, |n| = 1 within 1e-6), and the rotation into sponge space does not lengthen a displacement, so
+// every probe has box = max|q| - 1 >= 2.29 (roundings ~1e-5).  sponge_folds returns its d unchanged once d >= 1/3
+// (its first exit test, on every lane of the wave): the probe's distance is its box term, and the exit compare,
+// the ballot and the branch of each probe are not needed.  BOX = true states that (scene T only); the
+// instrumented kernels keep the folds' path and its counts.
 // common.frag:697-708 (tetrahedral gradient, h = 0.001)
-template <int SC, int NB = 3>
+template <int SC, int NB = 3, bool BOX = false>
 __device__ __forceinline__ V3 normal_fast(const FrameConst& F, V3 p, Tally& cnt, bool plane = false) {
+    static_assert(!BOX || SC == SCENE_T, "box-only probes: scene T's far-sky waves");
     const float h = 0.001f;
-    float d0 = dist_at<SC, kExactForm, NB>(F, p + v3(h, -h, -h), cnt, plane);
-    float d1 = dist_at<SC, kExactForm, NB>(F, p + v3(-h, -h, h), cnt, plane);
-    float d2 = dist_at<SC, kExactForm, NB>(F, p + v3(-h, h, -h), cnt, plane);
-    float d3 = dist_at<SC, kExactForm, NB>(F, p + v3(h, h, h), cnt, plane);
+    auto dist = [&](V3 q) {
+        if constexpr (BOX) return sponge_box(sponge_space<ScenePolicy<SC>::kExactMarch>(F, q));
+        else return dist_at<SC, kExactForm, NB>(F, q, cnt, plane);
+    };
+    float d0 = dist(p + v3(h, -h, -h));
+    float d1 = dist(p + v3(-h, -h, h));
+    float d2 = dist(p + v3(-h, h, -h));
+    float d3 = dist(p + v3(h, h, h));
     V3 g = v3(d0, -d0, -d0) + v3(-d1, -d1, d1);
     g = g + v3(-d2, d2, -d2);
     g = g + v3(d3, d3, d3);
@@ -318,24 +330,36 @@ __device__ __forceinline__ float soft_shadow2_T_loop(const FrameConst& F, const 
         cnt.evals++;
         cnt.flop += FL_LINRAY + FL_BOX;
         if constexpr (SM == 2) cnt.skipped += was_settled ? 1u : 0u;
+        // The settle gate's two lane masks are taken where their operands are at hand: box >= 0.1 before the folds
+        // raise the box term to h in place (box is not live across them; the settle block, which rarely runs, forms
+        // it again from q), h + h >= P where P is last read (the new P is the old one's only successor).  Each
+        // had cost a v_mov_b32 per step.
+        const bool bfar = box >= 0.1f;
+        const uint64_t m_far = SM != 0 ? __builtin_amdgcn_ballot_w64(bfar) : 0;
         h = sponge_folds<ScenePolicy<SCENE_T>::kExactMarch, NB>(q, box, cnt.flop);
         float h2 = h * h;
         float Q = it == 1 ? 1.0f : fmaf(P, P, -h2);
         float D = it == 1 ? t : fmaf(t, P, -h2);
+        const bool away = h + h >= P;
         float cn = h2 * Q, cd = D * fabsf(D);  // D <= 0: cd <= 0 fails the test (cn, den >= 0)
         bool upd = (Q >= 0.0f) & (cn * den < num * cd);
         num = upd ? cn : num;
         den = upd ? cd : den;
         bool settled = false;
         if constexpr (SM != 0) {
-            const bool any = (__builtin_amdgcn_ballot_w64(box >= 0.1f) & __builtin_amdgcn_ballot_w64(h + h >= P)) != 0;
+            const bool any = (m_far & __builtin_amdgcn_ballot_w64(away)) != 0;
             if (any) {
-                const float ax = fabsf(q.x), ay = fabsf(q.y), m = box + 1.0f;
-                const float sx = q.x < 0.0f ? -s.d.x : s.d.x, sy = q.y < 0.0f ? -s.d.y : s.d.y;
-                const float sz = q.z < 0.0f ? -s.d.z : s.d.z;
+                // sponge_box(q) again: the same operations, the same float (through an empty asm: left visible, the
+                // compiler reuses the step's own max and box and keeps both live across the folds)
+                float qx = q.x, qy = q.y, qz = q.z;
+                asm volatile("" : "+v"(qx), "+v"(qy), "+v"(qz));
+                const float ax = fabsf(qx), ay = fabsf(qy), m = fmaxf(ax, fmaxf(ay, fabsf(qz)));
+                const float box = m - 1.0f;
+                const float sx = qx < 0.0f ? -s.d.x : s.d.x, sy = qy < 0.0f ? -s.d.y : s.d.y;
+                const float sz = qz < 0.0f ? -s.d.z : s.d.z;
                 const float sl = ax == m ? sx : ay == m ? sy : sz;
                 const float be = fmaf(sl, maxt - t, box);
-                settled = (box >= 0.1f) & (h + h >= P) & (sl >= 0.0f) & (kSettleK * box * box * den >= num * t * t) &
+                settled = bfar & away & (sl >= 0.0f) & (kSettleK * box * box * den >= num * t * t) &
                           (kSettleK * be * be * den >= num * maxt * maxt);
             }
         }
@@ -407,13 +431,19 @@ __device__ __forceinline__ float dot_fma(V3 a, V3 b) { return fmaf(a.z, b.z, fma
 // sponge-space image (q0 + (R n) 0.2 (i + 1), one FMA per axis) instead of
 // transforming each probe point (the AO factor is smooth in the roundings;
 // step counts do not depend on it)
-template <int SC, int NB = 3>
+// BOX (scene T's far-sky waves, normal_fast above): the probes' distances are their box terms
+template <int SC, int NB = 3, bool BOX = false>
 __device__ __forceinline__ float ao_real(const FrameConst& F, V3 pos, V3 n, Tally& cnt, bool plane = false) {
+    static_assert(!BOX || SC == SCENE_T, "box-only probes: scene T's far-sky waves");
     float sum = 0.0f;
     if constexpr (SC == SCENE_T) {
         const LinRay r = sponge_ray(F, pos, n);
+        auto dist = [&](float t) {
+            if constexpr (BOX) return sponge_box(at(r, t));
+            else return menger_at<NB>(r, t, cnt);
+        };
 #pragma unroll
-        for (int i = 0; i < 4; i++) sum += (1.0f / (float)(1 << i)) * menger_at<NB>(r, (float)(i + 1) * 0.2f, cnt);
+        for (int i = 0; i < 4; i++) sum += (1.0f / (float)(1 << i)) * dist((float)(i + 1) * 0.2f);
         float maxSum = 0.0f;
 #pragma unroll
         for (int i = 0; i < 4; i++) maxSum += (1.0f / (float)(1 << i)) * (float)(i + 1) * 0.2f;
@@ -655,7 +685,11 @@ __device__ __forceinline__ V3 render_T_from(const FrameConst& F, const LinRay& p
     if (RSTOP != 1 || !far) depth = cast_ray_T<NB>(F, prim, cnt);
     if constexpr (RSTOP == 2) cnt.skipped += far ? cnt.evals - e0 : 0u;
     V3 p = ro + rd * depth;
-    V3 n = normal_fast<SC, NB>(F, p, cnt);
+    // (the timed kernels' far-sky waves: the normal's and the AO's probes as box terms, normal_fast's BOX)
+    const bool boxp = RSTOP == 1 && far;
+    V3 n;
+    if (boxp) n = normal_fast<SC, NB, true>(F, p, cnt);
+    else n = normal_fast<SC, NB>(F, p, cnt);
     float c = 1.0f;
     if (RSTOP != 1 || !far) {
         // getColorReflect (common.frag:991-1002); its dead nr normal is skipped
@@ -675,13 +709,24 @@ __device__ __forceinline__ V3 render_T_from(const FrameConst& F, const LinRay& p
     V3 Ld = lightPos - p;
     float ld2 = dot(Ld, Ld);
     V3 lightDir = Ld * __builtin_amdgcn_rsqf(ld2);
-    float occ = ao_real<SC, NB>(F, p, n, cnt);
+    float occ;
+    if (boxp) occ = ao_real<SC, NB, true>(F, p, n, cnt);
+    else occ = ao_real<SC, NB>(F, p, n, cnt);
     float sha = shadow_if_lit<RSTOP>(dot(lightDir, n), cnt, [&] {
         return soft_shadow2_T<NB, SETTLE>(F, sponge_ray(F, p, lightDir), 0.01f, __builtin_amdgcn_sqrtf(ld2), cnt);
     });
-    float sky = clamp01(0.5f + 0.5f * n.y);
-    float ind = clamp01(dot(n, mnormalize<SC>(lightDir * v3(-1.0f, 0.0f, -1.0f))));
-    float fre = clamp01(1.0f + dot(n, rd));
+    // The three clamps as clamp01_as (one v_med3_f32, folded into the clamp modifier of the instruction before
+    // it, instead of two compares and two selects each), in the form of DESIGN.md 2.17:
+    //   NaN: the median differs from GLSL's clamp only for a NaN argument, and the arguments (finite pos, rd,
+    //   lightDir) are NaN only when the normal n is.  Then the AO ray is built from n (sponge_ray(p, n)), every
+    //   coordinate of its probes' box term is NaN and occ is NaN; occ multiplies all three terms, and phong of a
+    //   NaN normal returns NaN (neither of its `< 0` tests holds): the shading is NaN in both forms.
+    //   Signed zero: med3 gives +0 where clamp01 gives -0.  The terms are added to phong's (a sum: the zero's
+    //   sign is lost unless every term is a zero), and the shading reaches the pixel only through color * (1 - e)
+    //   + fog * e with fog * e > 0 (apply_scattering: e = exp2(..) > 0), where a zero of either sign adds nothing.
+    float sky = clamp01_as<P::kTrim>(0.5f + 0.5f * n.y);
+    float ind = clamp01_as<P::kTrim>(dot(n, mnormalize<SC>(lightDir * v3(-1.0f, 0.0f, -1.0f))));
+    float fre = clamp01_as<P::kTrim>(1.0f + dot(n, rd));
     fre = fre * fre;  // pow(x, 2.0)
     // shadow_pow(1) is (1, 1, 1) exactly (v_log_f32(1) = 0, v_exp_f32(0) = 1), and sha is 1 on every lane that
     // took no shadow march or whose march met nothing: the log2 and the two exp2 only in waves with a shadowed lane
@@ -705,8 +750,13 @@ __device__ __forceinline__ V3 render_T(const FrameConst& F, V3 ro, V3 rd, Tally&
     // (in VGPRs, as the lanes' own results were: an SGPR addend makes the march's three FMAs per step the slow
     // issue form)
     asm volatile("" : "+v"(qx), "+v"(qy), "+v"(qz));
-    const LinRay prim{v3(qx, qy, qz), sponge_rot<ScenePolicy<SCENE_T>::kExactMarch>(F, rd.x, rd.y, rd.z)};
-    return render_T_from<NB, SETTLE, RSTOP>(F, prim, ro, rd, cnt);
+    // sponge_rot's four constants in VGPRs as well, for the pixel's eleven transforms (the normal's four probes,
+    // the AO, reflection, shadow and primary rays): the same instructions in the fast issue form; C3 0.3659-0.3678
+    // -> 0.3639-0.3653 ms, six alternating runs each.  G is F but for those four members.
+    FrameConst G = F;
+    asm volatile("" : "+v"(G.ry_c), "+v"(G.ry_s), "+v"(G.rx_c), "+v"(G.rx_s));
+    const LinRay prim{v3(qx, qy, qz), sponge_rot<ScenePolicy<SCENE_T>::kExactMarch>(G, rd.x, rd.y, rd.z)};
+    return render_T_from<NB, SETTLE, RSTOP>(G, prim, ro, rd, cnt);
 }
 
 // BASELINE config-1 scene S0: castRayD + normal + lambert
@@ -731,14 +781,16 @@ __device__ __forceinline__ V3 render_S0(const FrameConst& F, V3 ro, V3 rd, Tally
 template <bool FAST>
 __device__ __forceinline__ void camera_ray(const FrameConst& F, int x, int y, float& tcx, float& tcy, V3& ro, V3& rd) {
     if constexpr (FAST) {
-        tcx = ((float)x + 0.5f + F.jit_x) * __builtin_amdgcn_rcpf((float)F.W);
-        tcy = ((float)y + 0.5f + F.jit_y) * __builtin_amdgcn_rcpf((float)F.H);
+        // F.rcp_*: the v_rcp_f32 of (float)W, (float)H and res_y, computed on the device once per resolution
+        // (rm_render_host.cpp frame_rcp): the floats the three converts and reciprocals gave here in every wave
+        tcx = ((float)x + 0.5f + F.jit_x) * F.rcp_w;
+        tcy = ((float)y + 0.5f + F.jit_y) * F.rcp_h;
     } else {
         tcx = ((float)x + 0.5f + F.jit_x) / (float)F.W;  // (jitter 0 outside rm_render_accumulate*)
         tcy = ((float)y + 0.5f + F.jit_y) / (float)F.H;
     }
-    const float ux = FAST ? (tcx - 0.5f) * F.res_x * __builtin_amdgcn_rcpf(F.res_y) : (tcx - 0.5f) * F.res_x / F.res_y;
-    const float uy = FAST ? (tcy - 0.5f) * F.res_y * __builtin_amdgcn_rcpf(F.res_y) : (tcy - 0.5f) * F.res_y / F.res_y;
+    const float ux = FAST ? (tcx - 0.5f) * F.res_x * F.rcp_res_y : (tcx - 0.5f) * F.res_x / F.res_y;
+    const float uy = FAST ? (tcy - 0.5f) * F.res_y * F.rcp_res_y : (tcy - 0.5f) * F.res_y / F.res_y;
     ro = v3(F.pos_x, F.pos_y, F.pos_z);
     if constexpr (FAST) {
         // normalize() = a * (1 / sqrtf(dot)) compiles to the range-guarded sqrt (apply_scattering, TRIM) and a
@@ -792,6 +844,24 @@ __device__ __forceinline__ void store_pixel(const FrameConst& F, OUT* __restrict
 __device__ __forceinline__ int shard_row(const FrameConst& F, int j) {
     int c = div_by(j, F.run_magic, F.run), r = j - c * F.run;
     return c * F.cycle + F.offset + r;
+}
+// The same for a wave's rows row0 + jw + dl (jw wave-uniform, dl the lane's row in the wave), scenes S0/T
+// (ScenePolicy::kTileRow), by F.tile_run (the host's wave_row_mode, rm_rows.h):
+//   1  the part is every row of the frame (cycle = run, offset 0): c cycle + r = c run + r = j, no division;
+//   2  the wave's rows lie in one run: c is the wave's and r = r(row0 + jw) + dl, so y = shard_row(row0 + jw) + dl
+//      in integers -- the division once per wave on the scalar unit (s_mul_hi_u32; the host sets 2 only with a
+//      run_magic) instead of v_mul_hi_u32 and v_mul_lo per lane;
+//   0  any other layout (a band of 3, ragged parts, a part starting inside a wave's rows): the per-lane form.
+// UNIFORM: jw is wave-uniform as the compiler sees it (one-wave workgroups: the workgroup's first row)
+template <bool UNIFORM>
+__device__ __forceinline__ int shard_row_of_wave(const FrameConst& F, int jw, int dl) {
+    if (F.tile_run == 1) return F.row0 + jw + dl;
+    if (F.tile_run == 2) {
+        const int jb = F.row0 + (UNIFORM ? jw : __builtin_amdgcn_readfirstlane(jw));
+        const int c = (int)__umulhi((uint32_t)jb, F.run_magic);
+        return c * (F.cycle - F.run) + F.offset + jb + dl;  // c cycle + offset + (jb - c run) + dl
+    }
+    return shard_row(F, F.row0 + jw + dl);
 }
 
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
@@ -918,7 +988,10 @@ __device__ __forceinline__ void render_tile_at(const FrameConst& F, OUT* __restr
     uint32_t wire_px = 0;  // (kWire: this lane's RGBA8 word, 0 outside the part)
     Tally cnt;
     if (x < F.W && j < F.nrows) {
-        const int y = shard_row(F, F.row0 + j);
+        int y;
+        if constexpr (P::kTileRow)  // (one-wave workgroups: w = 0, the wave's first row is the workgroup's)
+            y = shard_row_of_wave<T::WPB == 1>(F, by * T::TH + (T::WPB == 1 ? 0 : (w >> 1) * 8), lane / T::LW);
+        else y = shard_row(F, F.row0 + j);
         float tcx, tcy;
         V3 ro, rd;
         camera_ray<P::kHwMath>(F, x, y, tcx, tcy, ro, rd);

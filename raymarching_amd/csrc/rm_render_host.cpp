@@ -138,13 +138,43 @@ FrameConst frame_const(const rm_ctx *c, int W, int H, const RowPart &part, int n
     return F;
 }
 
+rm_status frame_rcp(rm_ctx *ctx, FrameConst &F) {
+    if (ctx->scene != rm::SCENE_S0 && ctx->scene != rm::SCENE_T) return RM_OK;  // (the other scenes divide)
+    uint32_t bits;
+    std::memcpy(&bits, &F.res_y, sizeof(bits));
+    rm_ctx::RcpEntry *hit = nullptr, *lru = &ctx->rcp_cache[0];
+    for (int i = 0; i < ctx->rcp_n; i++) {
+        rm_ctx::RcpEntry &e = ctx->rcp_cache[i];
+        if (e.W == F.W && e.H == F.H && e.res_y_bits == bits) hit = &e;
+        if (e.used < lru->used) lru = &e;
+    }
+    if (!hit) {
+        if (!ctx->d_rcp) RM_HIP(hipMalloc(&ctx->d_rcp, 3 * sizeof(float)));
+        float v[3];
+        hipError_t e = rm::launch_resolution_rcp(F.W, F.H, F.res_y, ctx->d_rcp, ctx->stream);
+        if (e != hipSuccess) return hip_fail(ctx, e, "resolution reciprocal launch");
+        RM_HIP(hipMemcpyAsync(v, ctx->d_rcp, sizeof(v), hipMemcpyDeviceToHost, ctx->stream));
+        RM_HIP(hipStreamSynchronize(ctx->stream));
+        hit = ctx->rcp_n < rm_ctx::kRcpEntries ? &ctx->rcp_cache[ctx->rcp_n++] : lru;
+        hit->W = F.W; hit->H = F.H; hit->res_y_bits = bits;
+        std::memcpy(hit->rcp, v, sizeof(v));
+    }
+    hit->used = ++ctx->rcp_clock;
+    F.rcp_w = hit->rcp[0]; F.rcp_h = hit->rcp[1]; F.rcp_res_y = hit->rcp[2];
+    return RM_OK;
+}
+
 rm_status render_dev(rm_ctx *ctx, int W, int H, const RowPart &part, int row0, int count, void *out, bool rgba8,
                      rm_stats *stats, uint32_t *evmap, bool accum, const WireOut *wire) {
     rm::TraceRange range("rm_render");
     // the wire's tile code runs in one-wave 8x8 tiles (rm_render_direct.h)
     const int kernel = wire ? (int)rm::KERNEL_TILE8 : pick_kernel(ctx->params);
     FrameConst F = frame_const(ctx, W, H, part, count);
+    if (rm_status st = frame_rcp(ctx, F)) return st;
     F.row0 = row0;
+    // scenes S0/T: a wave's rows from one scalar division (waves are 8 rows high, 4 in the 16x4 tiling)
+    F.tile_run = rm::wave_row_mode(part, row0, kernel == rm::KERNEL_TILE16X4 ? 4 : 8, F.run_magic != 0);
+
     F.evals_map = evmap;
     if (accum) {  // fract(u_seed1) - 0.5 (GLSL fract, x - floor(x)), per frame
         F.accumulate = 1;

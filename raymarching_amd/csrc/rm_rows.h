@@ -19,6 +19,14 @@ inline bool cycle_part(int cycle, int offset, int run, RowPart &p) {
     p = RowPart{cycle, offset, run};
     return true;
 }
+// FrameConst.tile_run (rm_device.h; shard_row_of_wave, rm_render_direct.h): how packed rows row0 + [jb, jb + wave_h),
+// jb a multiple of wave_h, map to frame rows.  1: the part is every row of the frame (cycle = run, offset 0:
+// y = j); 2: they lie in one run (wave_h divides the run length and row0), and the launch divides by a magic
+// multiplier (has_magic); 0: neither, each lane finds its own row
+inline int wave_row_mode(const RowPart &p, int row0, int wave_h, bool has_magic) {
+    if (p.cycle == p.run && p.offset == 0) return 1;
+    return has_magic && p.run % wave_h == 0 && row0 % wave_h == 0 ? 2 : 0;
+}
 inline int rows_of_part(int H, const RowPart &p) {
     const long long full = H / p.cycle, rest = H - full * p.cycle;
     long long tail = rest - p.offset;

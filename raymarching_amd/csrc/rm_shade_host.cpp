@@ -91,6 +91,7 @@ rm_status rm_shade_rays(rm_ctx *ctx, const float *origins, int shared_origin, co
     // the ray image's size reaches the kernels for the vignette's texcoords only
     const int W = params->width > 0 ? params->width : 1, H = params->width > 0 ? (int)(n / params->width) : 1;
     FrameConst F = frame_const(ctx, W, H, RowPart{1, 0, 1}, H);
+    if (rm_status st = frame_rcp(ctx, F)) return st;
     if (shared_origin) {  // the launch's u_pos; scene T's primary rays start from its sponge-space image, as a frame's
         F.pos_x = origins[0];
         F.pos_y = origins[1];
