@@ -87,7 +87,8 @@ typedef struct rm_stats {
                         kernels do not execute (exact early exits whose results equal
                         the reference's: settled soft shadows, the soft shadows of
                         points facing away from the light, scene T's reflection march
-                        past depth 3); executed = evals - skipped */
+                        past depth 3); executed = evals - skipped -
+                        the count rm_certified_steps() returns */
     int32_t dispatch; /* RM_DISPATCH_*: the tile order this launch ran (ABI 3)           */
     int32_t lat_tiles; /* scene T: workgroups that rendered with the latency-optimized
                          fold tests (the costliest tiles at the head of an ordered
@@ -564,6 +565,15 @@ rm_status rm_post_chain_ex(rm_ctx *ctx, int W, int H, int sample, int tonemap, c
  * not.  entries: resolutions held now; capacity: the most it holds (the least
  * recently used one is replaced).  Either pointer may be NULL. */
 rm_status rm_resolution_cache_info(rm_ctx *ctx, int *entries, int *capacity);
+
+/* The certified ray-steps of this context's last render launch, if it filled an rm_stats with count_evals
+ * on (every render launch resets the count, so a launch without an rm_stats or without counting leaves 0,
+ * never an earlier launch's value): of its `evals`, and none of them in its `skipped`, the soft-shadow ray-steps of lit points whose
+ * shadow ray passes scene T's certificate (csrc/rm_shadow_clear.h).  The march is proved
+ * to return 1 and the uninstrumented kernels do not take it, so they execute evals - skipped - *steps.
+ * 0 for every other scene and for uncounted renders.  (A call of its own, not an rm_stats member:
+ * rm_stats keeps its layout and RM_ABI_VERSION its value.) */
+rm_status rm_certified_steps(rm_ctx *ctx, uint64_t *steps);
 
 /* The render kernels' code objects by content (16 hex digits of a SHA-256 of
  * the translation units that hold them): rocprofv3 counters of a render launch

@@ -189,6 +189,18 @@ class Renderer:
     def _ptr(t):
         return ctypes.c_void_p(t.data_ptr()) if hasattr(t, "data_ptr") else ctypes.c_void_p(t.ctypes.data)
 
+    def certified_steps(self) -> int:
+        """rm_certified_steps: of the last counted render's evals, the soft-shadow
+        ray-steps scene T's certificate proves away; 0 elsewhere."""
+        n = ctypes.c_uint64(0)
+        check(lib().rm_certified_steps(self._ctx, ctypes.byref(n)), self._ctx)
+        return int(n.value)
+
+    def _stats(self, s) -> dict:
+        """rm_stats as a dict, with `certified` (rm_certified_steps of the same call): every stats dict
+        made from an rm_stats carries the key (render_aa's is an rm_aa_stats: other members, no ray-step counts)"""
+        return dict(s.as_dict(), certified=self.certified_steps())
+
     def render(self, W: int, H: int, out=None, stats: bool = False):
         """Full frame into `out` (device tensor [H,W,4] f32; allocated if None)."""
         torch = _torch()
@@ -198,7 +210,7 @@ class Renderer:
         s = RmStats()
         check(lib().rm_render(self._ctx, int(W), int(H), self._ptr(out), ctypes.byref(s) if stats else None),
               self._ctx)
-        return (out, s.as_dict()) if stats else out
+        return (out, self._stats(s)) if stats else out
 
     def render_accumulate(self, W: int, H: int, accum, stats: bool = False):
         """Progressive accumulation (rm_render_accumulate[_rgba8]): `accum` holds
@@ -213,7 +225,7 @@ class Renderer:
         s = RmStats()
         fn = lib().rm_render_accumulate_rgba8 if rgba8 else lib().rm_render_accumulate
         check(fn(self._ctx, int(W), int(H), self._ptr(accum), ctypes.byref(s) if stats else None), self._ctx)
-        return (accum, s.as_dict()) if stats else accum
+        return (accum, self._stats(s)) if stats else accum
 
     def render_step_map(self, W: int, H: int, out=None, evals_map=None):
         """Full frame plus the per-pixel sceneSDF call counts: (float32 [H, W, 4],
@@ -229,7 +241,7 @@ class Renderer:
         s = RmStats()
         check(lib().rm_render_step_map(self._ctx, int(W), int(H), self._ptr(out), self._ptr(evals_map),
                                        ctypes.byref(s)), self._ctx)
-        return out, evals_map, s.as_dict()
+        return out, evals_map, self._stats(s)
 
     def render_band(self, W: int, H: int, band: int, nshards: int, shard: int, out=None, stats: bool = False):
         """Rows y with (y // band) % nshards == shard, packed in increasing y."""
@@ -241,7 +253,7 @@ class Renderer:
         s = RmStats()
         check(lib().rm_render_band(self._ctx, int(W), int(H), int(band), int(nshards), int(shard), self._ptr(out),
                                    ctypes.byref(s) if stats else None), self._ctx)
-        return (out, s.as_dict()) if stats else out
+        return (out, self._stats(s)) if stats else out
 
     def render_rows(self, W, H, band, nshards, shard, row_begin, row_count, out, stats=False):
         """Packed rows [row_begin, row_begin + row_count) of a shard into `out`
@@ -253,7 +265,7 @@ class Renderer:
         fn = lib().rm_render_rows_rgba8 if rgba8 else lib().rm_render_rows
         check(fn(self._ctx, int(W), int(H), int(band), int(nshards), int(shard), int(row_begin), int(row_count),
                  self._ptr(out), ctypes.byref(s) if stats else None), self._ctx)
-        return (out, s.as_dict()) if stats else out
+        return (out, self._stats(s)) if stats else out
 
     def render_cycle_rows(self, W, H, cycle, offset, run, row_begin, row_count, out, stats=False):
         """Packed rows [row_begin, row_begin + row_count) of the cyclic part
@@ -265,7 +277,7 @@ class Renderer:
         fn = lib().rm_render_cycle_rows_rgba8 if rgba8 else lib().rm_render_cycle_rows
         check(fn(self._ctx, int(W), int(H), int(cycle), int(offset), int(run), int(row_begin), int(row_count),
                  self._ptr(out), ctypes.byref(s) if stats else None), self._ctx)
-        return (out, s.as_dict()) if stats else out
+        return (out, self._stats(s)) if stats else out
 
     def deinterleave_cycle_rgb8(self, W, H, cycle, offsets, runs, part_bytes, gathered, out=None):
         """The RGBA8 frame (alpha 255) from cyclic parts' packed RGB8 rows:
@@ -308,7 +320,7 @@ class Renderer:
                                               int(row_begin), int(row_count), self._ptr(msg), self._ptr(workspace),
                                               self._ptr(size_out) if size_out is not None else None,
                                               ctypes.byref(s) if stats else None), self._ctx)
-        return (msg, s.as_dict()) if stats else msg
+        return (msg, self._stats(s)) if stats else msg
 
     def wire_encode(self, rows, msg, workspace, size_out=None):
         """Compressed wire of packed RGBA8 rows (int32 [n, W]) into the uint8
@@ -366,7 +378,7 @@ class Renderer:
         s = RmStats()
         check(lib().rm_render_band_rgba8(self._ctx, int(W), int(H), int(band), int(nshards), int(shard),
                                          self._ptr(out), ctypes.byref(s) if stats else None), self._ctx)
-        return (out, s.as_dict()) if stats else out
+        return (out, self._stats(s)) if stats else out
 
     def deinterleave(self, W, H, band, nshards, rows_per_shard, gathered, out=None):
         """gathered: [nshards, rows_per_shard, W, 4] f32, [nshards, rows_per_shard, W] RGBA8 words, or
@@ -557,7 +569,7 @@ class Renderer:
         check(lib().rm_cast_rays(self._ctx, self._ptr(o), int(shared), self._ptr(d), n, int(bool(inside)),
                                  ctypes.byref(hits), ctypes.byref(s) if stats else None), self._ctx)
         if stats:
-            out["stats"] = s.as_dict()
+            out["stats"] = self._stats(s)
         return out
 
     def camera_rays(self, W: int, H: int):
@@ -623,7 +635,7 @@ class Renderer:
         check(lib().rm_shade_rays(self._ctx, self._ptr(o), int(shared), self._ptr(d), n, ctypes.byref(p),
                                   None if rgba8 else self._ptr(out), self._ptr(out) if rgba8 else None,
                                   ctypes.byref(s) if stats else None), self._ctx)
-        return (out, s.as_dict()) if stats else out
+        return (out, self._stats(s)) if stats else out
 
     def render_rgba8(self, W, H, out=None, stats=False):
         torch = _torch()
@@ -633,7 +645,7 @@ class Renderer:
         s = RmStats()
         check(lib().rm_render_rgba8(self._ctx, W, H, self._ptr(out), ctypes.byref(s) if stats else None),
               self._ctx)
-        return (out, s.as_dict()) if stats else out
+        return (out, self._stats(s)) if stats else out
 
     # --- adaptive supersampling (rm_render_aa_rgba8, rm_refine_rgba8) -----
     def _aa(self, fn, W, H, samples, threshold, frame8, mask, stats):
@@ -763,7 +775,7 @@ class Comm:
                   self.r._ctx)
         else:
             check(lib().rm_render_sharded(self._h, int(W), int(H), int(band), fp, sp), self.r._ctx)
-        return (frame, s.as_dict()) if stats else frame
+        return (frame, self.r._stats(s)) if stats else frame
 
     @staticmethod
     def render_all(comms, W: int, H: int, band: int = 16, frame=None, stats: bool = False, runs=None):
@@ -784,7 +796,7 @@ class Comm:
         else:
             check(lib().rm_render_sharded_all(hs, n, int(W), int(H), int(band), comms[0].r._ptr(frame),
                                               st if stats else None), comms[0].r._ctx)
-        return (frame, [x.as_dict() for x in st]) if stats else frame
+        return (frame, [c.r._stats(x) for c, x in zip(comms, st)]) if stats else frame
 
     @property
     def uses_rccl(self) -> bool:

@@ -59,6 +59,7 @@ struct rm_ctx {
     std::string err;
     std::set<std::string> warned;
     unsigned long long *d_evals = nullptr;
+    unsigned long long last_certified = 0;  // rm_certified_steps(): d_evals[3] of the last render launch, 0 unless it was counted and filled an rm_stats
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float4 *staging = nullptr;
     size_t staging_bytes = 0;

@@ -24,6 +24,7 @@ using __hip_internal::uint64_t;
 #include <stdint.h>
 #endif
 #include "rm_far_sky.h"
+#include "rm_shadow_clear.h"
 
 namespace rm {
 
@@ -157,6 +158,10 @@ struct ScenePolicy {
     static constexpr bool kTileRow = kHwMath;
     // Scene T: the far-sky shortcut of render_T_from (rm_far_sky.h)
     static constexpr bool kFarSky = SC == SCENE_T;
+    // Scene T: lit lanes whose shadow ray passes rmsc::shadow_clear take no soft-shadow march
+    // (rm_shadow_clear.h).  Scene T's distance alone is bounded below by the sponge's box term
+    // along the whole ray; scene O's smooth min with its other objects is not.
+    static constexpr bool kShadowClear = SC == SCENE_T;
     // Minimum waves per SIMD the register allocator must allow.  Scene O asks
     // for 8 (64 VGPRs): its kernel needs ~82, and the few spills to scratch cost
     // less than occupancy 5 does (C5 frame 12.29 -> 11.56 ms,
@@ -267,6 +272,8 @@ struct Tally {
     uint32_t evals = 0;
     uint32_t flop = 0;
     uint32_t skipped = 0;  // of evals: steps the timed kernels leave out (exact early exits)
+    uint32_t certified = 0;  // of evals, none of them in skipped: the soft-shadow steps of lit lanes that pass
+                             // rmsc::shadow_clear, which the timed kernels leave out (scene T)
 };
 constexpr uint32_t FL_SPHERE = 9;      // sphere(): sub 3, dot 5, sub 1 (+ sqrt)
 constexpr uint32_t FL_TRANSFORM = 18;  // p - (0,3,0): 3; transformR's 3x3 rotation: 15

@@ -712,9 +712,35 @@ __device__ __forceinline__ V3 render_T_from(const FrameConst& F, const LinRay& p
     float occ;
     if (boxp) occ = ao_real<SC, NB, true>(F, p, n, cnt);
     else occ = ao_real<SC, NB>(F, p, n, cnt);
-    float sha = shadow_if_lit<RSTOP>(dot(lightDir, n), cnt, [&] {
-        return soft_shadow2_T<NB, SETTLE>(F, sponge_ray(F, p, lightDir), 0.01f, __builtin_amdgcn_sqrtf(ld2), cnt);
-    });
+    // The shadow certificate (rm_shadow_clear.h states the proof): a lit lane whose shadow ray
+    // leaves a face of the sponge's cube outward at a slope >= kRatio gets exactly 1.0f from the march, whatever
+    // its steps.  With RSTOP's modes, as shadow_if_lit's: 1 (timed kernels) such a lane does not march -- the test
+    // runs inside the lit branch only, and a wave whose lit lanes are all clear leaves the loop's exec mask empty
+    // and branches over it; 2 (instrumented) takes the march and counts in cnt.certified those of its steps that
+    // are not in cnt.skipped already (an unlit lane's steps stay in skipped, clear or not, and so do a clear
+    // lane's steps after its settle point); 0 marches.
+    const LinRay sray = sponge_ray(F, p, lightDir);
+    const float smint = 0.01f, smaxt = __builtin_amdgcn_sqrtf(ld2);
+    const float dotLN = dot(lightDir, n);
+    float sha;
+    if constexpr (P::kShadowClear && RSTOP == 1) {
+        sha = 1.0f;
+        if (!(dotLN < 0.0f)) {
+            if (!rmsc::shadow_clear(sray.o.x, sray.o.y, sray.o.z, sray.d.x, sray.d.y, sray.d.z, smint))
+                sha = soft_shadow2_T<NB, SETTLE>(F, sray, smint, smaxt, cnt);
+        }
+    } else {
+        const uint32_t e2 = cnt.evals, s2 = cnt.skipped;
+        sha = shadow_if_lit<RSTOP>(dotLN, cnt, [&] { return soft_shadow2_T<NB, SETTLE>(F, sray, smint, smaxt, cnt); });
+        if constexpr (P::kShadowClear && RSTOP == 2) {
+            const bool clear = !(dotLN < 0.0f) &&
+                               rmsc::shadow_clear(sray.o.x, sray.o.y, sray.o.z, sray.d.x, sray.d.y, sray.d.z, smint);
+            // the march's steps less those it already put into cnt.skipped (the steps after its settle point,
+            // SETTLE == 2): what the timed kernels would have executed of it, so the two counts never overlap
+            cnt.certified += clear ? (cnt.evals - e2) - (cnt.skipped - s2) : 0u;
+        }
+        (void)e2; (void)s2;
+    }
     // The three clamps as clamp01_as (one v_med3_f32, folded into the clamp modifier of the instruction before
     // it, instead of two compares and two selects each), in the form of DESIGN.md 2.17:
     //   NaN: the median differs from GLSL's clamp only for a NaN argument, and the arguments (finite pos, rd,
@@ -881,15 +907,17 @@ __device__ __forceinline__ uint32_t tile_clocks(uint64_t t_start) {
     return dt > 0xffffffffull ? 0xffffffffu : (uint32_t)dt;
 }
 // instrumented launches: pixel (x, packed row j)'s ray-steps into the step map,
-// the wave's tallies into evals[0..2]
+// the wave's tallies into evals[0..3]
 __device__ __forceinline__ void store_tally(const FrameConst& F, unsigned long long* evals, const Tally& cnt, int x,
                                             int j, int lane) {
     if (F.evals_map && x < F.W && j < F.nrows) F.evals_map[(size_t)j * F.W + x] = cnt.evals;
     uint32_t se = wave_sum_u32(cnt.evals), sf = wave_sum_u32(cnt.flop), ss = wave_sum_u32(cnt.skipped);
+    uint32_t sc = wave_sum_u32(cnt.certified);
     if (lane == 0) {
         atomicAdd(&evals[0], (unsigned long long)se);
         atomicAdd(&evals[1], (unsigned long long)sf);
         if (ss) atomicAdd(&evals[2], (unsigned long long)ss);
+        if (sc) atomicAdd(&evals[3], (unsigned long long)sc);
     }
 }
 
@@ -958,7 +986,7 @@ template <> struct Tiling<KERNEL_PERSIST> : Tiling<KERNEL_TILE8> {};
 // OUT = float4 (gl_FragColor) or uint32_t (RGBA8, packed in the epilogue, so
 // the displayed frame costs 4 B/px of HBM instead of 16 + 20 for a pack
 // pass).  COUNT: instrumented build, ray-steps and FLOP summed per wave into
-// evals[0..2] (ray-steps, FLOP, ray-steps the timed kernels skip).
+// evals[0..3] (ray-steps, FLOP, ray-steps the timed kernels skip by an early exit, and by the shadow certificate).
 // (bx, by): the tile's position in dispatch order on a gx-wide tile grid
 // (blockIdx for the hardware-dispatched kernels).
 template <int SC, bool COUNT, int K, typename OUT>

@@ -33,6 +33,7 @@ rm_status shade_dev(rm_ctx *ctx, const FrameConst &F, const rm::ShadeRays &Q, rm
         RM_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
         std::memset(stats, 0, sizeof(*stats));
         stats->pixels = (uint64_t)Q.n;
+        ctx->last_certified = 0;  // (rm_certified_steps: the shade kernels are not instrumented)
         stats->kernel_ms = ms;
         stats->scene = ctx->scene;
     }

@@ -723,7 +723,7 @@ class DeltaFrame(_ShardedFrame):
                              (self.r._ctx, p.W, p.H, *self._part, 0, self.nmine, self.msg[slot].data_ptr(),
                               self.ws[slot].data_ptr(), self.size_dev[slot].data_ptr(),
                               ctypes.byref(s) if stats else None))
-                return s.as_dict() if stats else None
+                return self.r._stats(s) if stats else None
             except RmError as e:
                 if "built-in scenes only" not in str(e):
                     raise

@@ -20,8 +20,15 @@ Per launch of the render kernel:
   executed_ray_steps_per_launch = config.executed_ray_steps_per_frame of the
       bench line the same command printed (BENCH_LOG: a file whose last JSON
       line is bench.py's), so bench.py can price a rank's share of the frame
-      (N > 1) or a walk's poses per executed ray-step
-usage: make_traffic_json.py SUMMARY.json KEY KERNEL_SUBSTR KERNEL_STATS.csv [OUT] [BENCH_LOG]
+      (N > 1) or a walk's poses per executed ray-step.  bench.py subtracts
+      rm_stats.skipped only, so this figure still holds the steps scene T's
+      shadow certificate leaves out; it stays in bench.py's
+      terms because bench.py scales by the ratio of its own figure to this one
+  certified_ray_steps_per_launch = rm_certified_steps() of the same frame
+      (CERTIFIED, from an instrumented render), and
+  marched_ray_steps_per_launch = evals - skipped - certified: the ray-steps the
+      counted launch really executed
+usage: make_traffic_json.py SUMMARY.json KEY KERNEL_SUBSTR KERNEL_STATS.csv [OUT] [BENCH_LOG] [CERTIFIED]
 """
 import csv
 import json
@@ -30,7 +37,8 @@ import sys
 
 summ, key, ksub, stats = sys.argv[1:5]
 out = sys.argv[5] if len(sys.argv) > 5 and sys.argv[5] else "profiles/pmc_counters.json"
-bench_log = sys.argv[6] if len(sys.argv) > 6 else None
+bench_log = sys.argv[6] if len(sys.argv) > 6 and sys.argv[6] else None
+certified = int(sys.argv[7]) if len(sys.argv) > 7 else None
 d = json.load(open(summ))
 k = [n for n in d if ksub in n][0]
 v = d[k]
@@ -62,6 +70,9 @@ if bench_log:
     line = [ln for ln in open(bench_log) if ln.startswith("{") and '"metric"' in ln][-1]
     entry["executed_ray_steps_per_launch"] = int(json.loads(line)["config"]["executed_ray_steps_per_frame"])
     entry["executed_ray_steps_source"] = os.path.relpath(bench_log)
+    if certified is not None:
+        entry["certified_ray_steps_per_launch"] = certified
+        entry["marched_ray_steps_per_launch"] = entry["executed_ray_steps_per_launch"] - certified
 if "GRBM_GUI_ACTIVE" in v:
     entry["clock_hz"] = v["GRBM_GUI_ACTIVE"] / 8 / (avg_ns * 1e-9)
 allj = json.load(open(out)) if os.path.exists(out) else {}
