@@ -88,7 +88,7 @@ typedef struct rm_stats {
                         the reference's: settled soft shadows, the soft shadows of
                         points facing away from the light, scene T's reflection march
                         past depth 3); executed = evals - skipped -
-                        the count rm_certified_steps() returns */
+                        the counts rm_certified_steps() and rm_reflection_cleared_steps() return */
     int32_t dispatch; /* RM_DISPATCH_*: the tile order this launch ran (ABI 3)           */
     int32_t lat_tiles; /* scene T: workgroups that rendered with the latency-optimized
                          fold tests (the costliest tiles at the head of an ordered
@@ -574,6 +574,16 @@ rm_status rm_resolution_cache_info(rm_ctx *ctx, int *entries, int *capacity);
  * 0 for every other scene and for uncounted renders.  (A call of its own, not an rm_stats member:
  * rm_stats keeps its layout and RM_ABI_VERSION its value.) */
 rm_status rm_certified_steps(rm_ctx *ctx, uint64_t *steps);
+
+/* The reflection ray-steps scene T's reflection certificate proves away, of this context's last render launch
+ * (counted and reset as rm_certified_steps' count is): of its `evals`, and none of them in its `skipped` or in
+ * rm_certified_steps' count, the steps begun at a depth < 3 of the reflection marches of lanes that hit the
+ * sponge and whose reflection ray passes the certificate (csrc/rm_refl_clear.h), outside far-sky
+ * waves.  With max_steps >= 28 the march is proved to meet nothing and to pass depth 3, where its factor is 1,
+ * and the uninstrumented kernels do not take it; under a smaller step cap they march and the count is 0.  (A
+ * sky lane of a mixed wave may pass the test as well; its one or two steps are not in the count.)  0 for every
+ * other scene and for uncounted renders.  A call of its own, as rm_certified_steps: rm_stats keeps its layout. */
+rm_status rm_reflection_cleared_steps(rm_ctx *ctx, uint64_t *steps);
 
 /* The render kernels' code objects by content (16 hex digits of a SHA-256 of
  * the translation units that hold them): rocprofv3 counters of a render launch

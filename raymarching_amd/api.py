@@ -196,10 +196,18 @@ class Renderer:
         check(lib().rm_certified_steps(self._ctx, ctypes.byref(n)), self._ctx)
         return int(n.value)
 
+    def reflection_cleared_steps(self) -> int:
+        """rm_reflection_cleared_steps: of the last counted render's evals, the reflection-march
+        ray-steps scene T's reflection certificate proves away; 0 elsewhere."""
+        n = ctypes.c_uint64(0)
+        check(lib().rm_reflection_cleared_steps(self._ctx, ctypes.byref(n)), self._ctx)
+        return int(n.value)
+
     def _stats(self, s) -> dict:
-        """rm_stats as a dict, with `certified` (rm_certified_steps of the same call): every stats dict
+        """rm_stats as a dict, with `certified` (rm_certified_steps of the same call) and `reflection_cleared`
+        (rm_reflection_cleared_steps): every stats dict
         made from an rm_stats carries the key (render_aa's is an rm_aa_stats: other members, no ray-step counts)"""
-        return dict(s.as_dict(), certified=self.certified_steps())
+        return dict(s.as_dict(), certified=self.certified_steps(), reflection_cleared=self.reflection_cleared_steps())
 
     def render(self, W: int, H: int, out=None, stats: bool = False):
         """Full frame into `out` (device tensor [H,W,4] f32; allocated if None)."""

@@ -60,6 +60,7 @@ struct rm_ctx {
     std::set<std::string> warned;
     unsigned long long *d_evals = nullptr;
     unsigned long long last_certified = 0;  // rm_certified_steps(): d_evals[3] of the last render launch, 0 unless it was counted and filled an rm_stats
+    unsigned long long last_refl_cleared = 0;  // rm_reflection_cleared_steps(): d_evals[4] of the last render launch, as last_certified
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float4 *staging = nullptr;
     size_t staging_bytes = 0;

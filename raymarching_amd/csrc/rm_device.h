@@ -25,6 +25,7 @@ using __hip_internal::uint64_t;
 #endif
 #include "rm_far_sky.h"
 #include "rm_shadow_clear.h"
+#include "rm_refl_clear.h"
 
 namespace rm {
 
@@ -84,6 +85,7 @@ struct FrameConst {
                                     // inside a wave's rows): each lane divides
 };
 static_assert(rmfs::kFarSkyDepth == ZFAR, "rm_far_sky.h restates ZFAR");
+static_assert(rmrc::kNear == ZNEAR, "rm_refl_clear.h restates ZNEAR");
 
 // FrameConst.camq_*: sponge_space<false>(F, u_pos) below, FMA for FMA (each one
 // rounding, on the host as on the device), so that scene T's lanes do not each
@@ -162,6 +164,9 @@ struct ScenePolicy {
     // (rm_shadow_clear.h).  Scene T's distance alone is bounded below by the sponge's box term
     // along the whole ray; scene O's smooth min with its other objects is not.
     static constexpr bool kShadowClear = SC == SCENE_T;
+    // Scene T: lanes whose reflection ray passes rmrc::refl_clear take no reflection march when the step cap
+    // is >= rmrc::kSteps (rm_refl_clear.h).  Scene O's reflection is a full shaded bounce, not a factor.
+    static constexpr bool kReflClear = SC == SCENE_T;
     // Minimum waves per SIMD the register allocator must allow.  Scene O asks
     // for 8 (64 VGPRs): its kernel needs ~82, and the few spills to scratch cost
     // less than occupancy 5 does (C5 frame 12.29 -> 11.56 ms,
@@ -274,6 +279,8 @@ struct Tally {
     uint32_t skipped = 0;  // of evals: steps the timed kernels leave out (exact early exits)
     uint32_t certified = 0;  // of evals, none of them in skipped: the soft-shadow steps of lit lanes that pass
                              // rmsc::shadow_clear, which the timed kernels leave out (scene T)
+    uint32_t refl_cleared = 0;  // of evals, none of them in skipped or certified: the reflection-march steps of
+                                // hit lanes that pass rmrc::refl_clear, which the timed kernels leave out (scene T)
 };
 constexpr uint32_t FL_SPHERE = 9;      // sphere(): sub 3, dot 5, sub 1 (+ sqrt)
 constexpr uint32_t FL_TRANSFORM = 18;  // p - (0,3,0): 3; transformR's 3x3 rotation: 15

@@ -696,13 +696,36 @@ __device__ __forceinline__ V3 render_T_from(const FrameConst& F, const LinRay& p
         const uint32_t e1 = cnt.evals, s1 = cnt.skipped;
         V3 rdir = reflect(rd, n);
         V3 ror = p + rdir * 0.01f;
-        V3 pr = ror + rdir * cast_ray_T<NB, RSTOP>(F, sponge_ray(F, ror, rdir), cnt);
-        if constexpr (RSTOP == 2) cnt.skipped = far ? s1 + (cnt.evals - e1) : cnt.skipped;
+        const LinRay rray = sponge_ray(F, ror, rdir);
+        // The reflection certificate (rm_refl_clear.h states the proof): a reflection ray that
+        // leaves a face of the sponge's cube outward at a slope >= kRatio meets nothing and passes depth 3 within
+        // kSteps steps, so with max_steps >= kSteps (a uniform compare: a smaller cap marches as before) its
+        // factor c is exactly 1.0f.  With RSTOP's modes: 1 (timed kernels) such a lane does not march -- a wave
+        // whose lanes are all clear leaves the loop's exec mask empty and branches over it, pr, pd and the sqrt;
+        // 2 (instrumented) takes the march and counts in cnt.refl_cleared those of its steps that are in neither
+        // cnt.skipped (the steps from depth 3 on; every step of a far-sky wave) nor cnt.certified, for the lanes
+        // that hit the sponge; 0 marches.
+        bool rclear = false;
+        if constexpr (P::kReflClear && RSTOP != 0)
+            rclear = (F.max_steps >= rmrc::kSteps) &
+                     rmrc::refl_clear(rray.o.x, rray.o.y, rray.o.z, rray.d.x, rray.d.y, rray.d.z);
+        if (RSTOP != 1 || !rclear) {
+            V3 pr = ror + rdir * cast_ray_T<NB, RSTOP>(F, rray, cnt);
+            if constexpr (RSTOP == 2) {
+                cnt.skipped = far ? s1 + (cnt.evals - e1) : cnt.skipped;
+                // counted for the lanes whose primary march ended in a hit (the distance at its last point again,
+                // into a tally nobody reads): a sky lane that passes the test marches a step or two from its far
+                // point, and those stay uncounted, so that a frame without a hit counts 0 under every step cap
+                Tally none;
+                const bool phit = menger_at<NB>(prim, depth, none) < 0.001f;
+                cnt.refl_cleared += rclear && phit ? (cnt.evals - e1) - (cnt.skipped - s1) : 0u;
+            }
+            // |pr - p| >= 0.01 (the offset of ror; the march adds depth >= ZNEAR along rdir): far above 2^-96, below
+            // which alone sqrtf's rescaling acts, so the bare v_sqrt_f32 is length()'s float (apply_scattering, TRIM)
+            const V3 pd = pr - p;
+            c = clamp01_as<P::kTrim>(__builtin_amdgcn_sqrtf(dot(pd, pd)) * (1.0f / 3.0f));
+        }
         (void)e1; (void)s1;
-        // |pr - p| >= 0.01 (the offset of ror; the march adds depth >= ZNEAR along rdir): far above 2^-96, below
-        // which alone sqrtf's rescaling acts, so the bare v_sqrt_f32 is length()'s float (apply_scattering, TRIM)
-        const V3 pd = pr - p;
-        c = clamp01_as<P::kTrim>(__builtin_amdgcn_sqrtf(dot(pd, pd)) * (1.0f / 3.0f));
     }
     (void)e0;
     const V3 lightPos = v3(20.0f, 50.0f, 0.0f);
@@ -907,17 +930,18 @@ __device__ __forceinline__ uint32_t tile_clocks(uint64_t t_start) {
     return dt > 0xffffffffull ? 0xffffffffu : (uint32_t)dt;
 }
 // instrumented launches: pixel (x, packed row j)'s ray-steps into the step map,
-// the wave's tallies into evals[0..3]
+// the wave's tallies into evals[0..4]
 __device__ __forceinline__ void store_tally(const FrameConst& F, unsigned long long* evals, const Tally& cnt, int x,
                                             int j, int lane) {
     if (F.evals_map && x < F.W && j < F.nrows) F.evals_map[(size_t)j * F.W + x] = cnt.evals;
     uint32_t se = wave_sum_u32(cnt.evals), sf = wave_sum_u32(cnt.flop), ss = wave_sum_u32(cnt.skipped);
-    uint32_t sc = wave_sum_u32(cnt.certified);
+    uint32_t sc = wave_sum_u32(cnt.certified), sr = wave_sum_u32(cnt.refl_cleared);
     if (lane == 0) {
         atomicAdd(&evals[0], (unsigned long long)se);
         atomicAdd(&evals[1], (unsigned long long)sf);
         if (ss) atomicAdd(&evals[2], (unsigned long long)ss);
         if (sc) atomicAdd(&evals[3], (unsigned long long)sc);
+        if (sr) atomicAdd(&evals[4], (unsigned long long)sr);
     }
 }
 
@@ -986,7 +1010,7 @@ template <> struct Tiling<KERNEL_PERSIST> : Tiling<KERNEL_TILE8> {};
 // OUT = float4 (gl_FragColor) or uint32_t (RGBA8, packed in the epilogue, so
 // the displayed frame costs 4 B/px of HBM instead of 16 + 20 for a pack
 // pass).  COUNT: instrumented build, ray-steps and FLOP summed per wave into
-// evals[0..3] (ray-steps, FLOP, ray-steps the timed kernels skip by an early exit, and by the shadow certificate).
+// evals[0..4] (ray-steps, FLOP, ray-steps the timed kernels skip by an early exit, by the shadow certificate, and by the reflection certificate).
 // (bx, by): the tile's position in dispatch order on a gx-wide tile grid
 // (blockIdx for the hardware-dispatched kernels).
 template <int SC, bool COUNT, int K, typename OUT>

@@ -212,8 +212,9 @@ rm_status render_dev(rm_ctx *ctx, int W, int H, const RowPart &part, int row0, i
         F.persist = pb->ctr;
     }
     ctx->last_certified = 0;  // rm_certified_steps(): of this launch alone, set below when it is counted
+    ctx->last_refl_cleared = 0;  // rm_reflection_cleared_steps(): likewise
     bool cnt = ctx->params.count_evals != 0 || evmap;
-    if (cnt) RM_HIP(hipMemsetAsync(ctx->d_evals, 0, 4 * sizeof(unsigned long long), ctx->stream));
+    if (cnt) RM_HIP(hipMemsetAsync(ctx->d_evals, 0, 5 * sizeof(unsigned long long), ctx->stream));
     if (stats) RM_HIP(hipEventRecord(ctx->ev0, ctx->stream));
     hipError_t e =
         wire ? rm::launch_render_wire(ctx->scene, F, static_cast<rm::WireTile *>(out), cnt ? ctx->d_evals : nullptr,
@@ -245,13 +246,14 @@ rm_status render_dev(rm_ctx *ctx, int W, int H, const RowPart &part, int row0, i
         RM_HIP(hipEventSynchronize(ctx->ev1));
         float ms = 0.0f;
         RM_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-        unsigned long long ev[4] = {0, 0, 0, 0};
+        unsigned long long ev[5] = {0, 0, 0, 0, 0};
         if (cnt) RM_HIP(hipMemcpy(ev, ctx->d_evals, sizeof(ev), hipMemcpyDeviceToHost));
         std::memset(stats, 0, sizeof(*stats));
         stats->evals = ev[0];
         stats->flop = ev[1];
         stats->skipped = ev[2];
         ctx->last_certified = ev[3];  // (0 when not counted)
+        ctx->last_refl_cleared = ev[4];
         stats->pixels = (uint64_t)W * (uint64_t)count;
         stats->kernel_ms = ms;
         stats->scene = ctx->scene;

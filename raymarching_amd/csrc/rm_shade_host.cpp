@@ -34,6 +34,7 @@ rm_status shade_dev(rm_ctx *ctx, const FrameConst &F, const rm::ShadeRays &Q, rm
         std::memset(stats, 0, sizeof(*stats));
         stats->pixels = (uint64_t)Q.n;
         ctx->last_certified = 0;  // (rm_certified_steps: the shade kernels are not instrumented)
+        ctx->last_refl_cleared = 0;
         stats->kernel_ms = ms;
         stats->scene = ctx->scene;
     }
