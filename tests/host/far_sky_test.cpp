@@ -18,6 +18,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <initializer_list>
 #include <limits>
 #include <utility>
@@ -345,7 +346,52 @@ static void step_bound() {
     CHECK(rmfs::kFarSkyDepth == ZFAR);
 }
 
-int main() {
+// far_sky_test --eval in.bin out.bin: n rays of 6 floats (ox oy oz dx dy dz, sponge space) -> n bytes of
+// rmfs::far_sky_ray, for tests/test_far_sky_host.py to hold tests/far_sky_ref.py's numpy restatement to
+static int eval_file(const char *in_path, const char *out_path) {
+    std::FILE *in = std::fopen(in_path, "rb");
+    if (!in) {
+        std::fprintf(stderr, "far_sky_test: cannot read %s\n", in_path);
+        return 2;
+    }
+    std::FILE *out = std::fopen(out_path, "wb");
+    if (!out) {
+        std::fprintf(stderr, "far_sky_test: cannot write %s\n", out_path);
+        std::fclose(in);
+        return 2;
+    }
+    float v[6];
+    long n = 0, accepted = 0;
+    int rc = 0;
+    for (;;) {
+        const size_t got = std::fread(v, sizeof(float), 6, in);
+        if (got == 0) break;
+        if (got != 6) {
+            std::fprintf(stderr, "far_sky_test: %s is not a whole number of rays\n", in_path);
+            rc = 2;
+            break;
+        }
+        const unsigned char b = rmfs::far_sky_ray(v[0], v[1], v[2], v[3], v[4], v[5]) ? 1 : 0;
+        if (std::fwrite(&b, 1, 1, out) != 1) {
+            std::fprintf(stderr, "far_sky_test: short write to %s\n", out_path);
+            rc = 2;
+            break;
+        }
+        n++;
+        accepted += b;
+    }
+    std::fclose(in);
+    if (std::fclose(out) != 0) rc = 2;
+    if (rc == 0) std::printf("evaluated %ld rays, %ld far-sky\n", n, accepted);
+    return rc;
+}
+
+int main(int argc, char **argv) {
+    if (argc == 4 && std::strcmp(argv[1], "--eval") == 0) return eval_file(argv[2], argv[3]);
+    if (argc != 1) {
+        std::fprintf(stderr, "usage: far_sky_test [--eval in.bin out.bin]\n");
+        return 2;
+    }
     step_bound();
     directed_rays();
     random_rays();

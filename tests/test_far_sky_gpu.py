@@ -9,8 +9,11 @@ instrumented frame in every bit: float4 and RGBA8, for the tile8, tile16 and
 persistent kernels, row-major and in adaptive order with scene T's latency
 tiles, at sizes with partly filled waves, with max_steps one below N0 (shortcut
 off), at N0 and at 256, on poses where no wave, some waves and every wave
-qualifies.  rm_shade_rays and rm_render_aa_rgba8 run the same render_T_from and
-are held to the references their own tests use.
+qualifies.  rm_shade_rays and rm_render_aa_rgba8 run the same render_T_from;
+here they run at 256 steps on the all_sky pose only, and their own tests
+(tests/test_shade_rays.py, tests/test_aa_gpu.py) at 128 steps, below N0.  With
+the shortcut live they are held to instrumented frames, ray by ray with origins
+per ray and in mixed waves, by tests/test_shade_rays_shortcuts.py.
 """
 import math
 
