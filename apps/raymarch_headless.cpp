@@ -19,7 +19,13 @@
 //          [--post] [--post-sample fxaa|chromatic|texel]
 //          [--tonemap none|aces|reinhard|jodie|uncharted2]
 //          [--uniform name=v[,v...]]... [--pick X,Y] [--aa K[:threshold]]
-//          [--fisheye fov_deg]
+//          [--fisheye fov_deg] [--views FILE]
+// --views FILE renders one view batch instead of the frame loop
+// (rm::Shader::renderBatch -> rm_render_batch_rgba8): FILE holds one view per
+// line, px py pz mx my t [ox oy] (u_pos, u_mouse, u_time and an optional
+// sub-pixel offset), all rendered at --w x --h by one launch on one GPU.  With
+// --ppm NAME it writes NAME.0000.ppm, NAME.0001.ppm, ...; with --stats the JSON
+// line carries the launch's kernel_ms.
 // --fisheye fov_deg writes --ppm from the fisheye camera main() carries
 // commented out (output_shader.frag:396-400) instead of the pinhole's frame:
 // after the last frame its w x h rays are built here on the host, from the
@@ -61,8 +67,52 @@
 
 #include "../include/rm_pass.hpp"
 
+// a w x h RGBA8 frame (R in the low byte) as a binary PPM
+static bool write_ppm(const std::string& name, const uint32_t* px, int w, int h) {
+    FILE* fp = std::fopen(name.c_str(), "wb");
+    if (!fp) return false;
+    std::fprintf(fp, "P6\n%d %d\n255\n", w, h);
+    for (size_t i = 0; i < (size_t)w * h; i++) {
+        const uint32_t v = px[i];
+        unsigned char rgb[3] = {(unsigned char)(v & 255), (unsigned char)((v >> 8) & 255),
+                                (unsigned char)((v >> 16) & 255)};
+        std::fwrite(rgb, 1, 3, fp);
+    }
+    return std::fclose(fp) == 0;
+}
+
+// --views FILE: one view per line, px py pz mx my t [ox oy]; empty lines and lines starting with '#' are skipped
+static bool read_views(const std::string& file, std::vector<rm_view>& views) {
+    FILE* fp = std::fopen(file.c_str(), "r");
+    if (!fp) {
+        std::fprintf(stderr, "--views: cannot open %s\n", file.c_str());
+        return false;
+    }
+    char line[512];
+    int lineno = 0;
+    bool ok = true;
+    while (ok && std::fgets(line, sizeof(line), fp)) {
+        lineno++;
+        const char* p = line;
+        while (*p == ' ' || *p == '\t') p++;
+        if (*p == '#' || *p == '\n' || *p == '\r' || *p == '\0') continue;
+        rm_view v;
+        std::memset(&v, 0, sizeof(v));
+        char tail = 0;
+        const int got = std::sscanf(p, "%f %f %f %f %f %f %f %f %c", &v.pos[0], &v.pos[1], &v.pos[2], &v.mouse[0],
+                                    &v.mouse[1], &v.time, &v.offset[0], &v.offset[1], &tail);
+        if (got != 6 && got != 8) {
+            std::fprintf(stderr, "--views %s:%d: expected px py pz mx my t [ox oy]\n", file.c_str(), lineno);
+            ok = false;
+        }
+        views.push_back(v);
+    }
+    std::fclose(fp);
+    return ok;
+}
+
 int main(int argc, char** argv) {
-    std::string scene = "output_shader.frag", script, ppm;
+    std::string scene = "output_shader.frag", script, ppm, views_file;
     int w = 1600, h = 900, frames = 60, steps = 128, gpus = 1, band = 16;
     int mdx = 0, mdy = 0;
     bool time_freeze = false, sharded = false, accumulate = false, stats = false, fmt_float = false;
@@ -99,6 +149,7 @@ int main(int argc, char** argv) {
         else if (a == "--gpus") gpus = std::atoi(next().c_str());
         else if (a == "--band") band = std::atoi(next().c_str());
         else if (a == "--ppm") ppm = next();
+        else if (a == "--views") views_file = next();
         else if (a == "--time-freeze") time_freeze = true;
         else if (a == "--sharded") sharded = true;
         else if (a == "--accumulate") accumulate = true;
@@ -240,6 +291,30 @@ int main(int argc, char** argv) {
         all.push_back(&s);
     }
     rm::Shader& shader = *all[0];
+    if (!views_file.empty()) {  // one batch instead of the frame loop
+        std::vector<rm_view> views;
+        if (!read_views(views_file, views)) return 2;
+        const int n = (int)views.size();
+        std::vector<uint32_t> px((size_t)n * w * h);  // a host target: staged, written when the call returns
+        rm_stats st;
+        std::memset(&st, 0, sizeof(st));
+        const auto b0 = std::chrono::steady_clock::now();
+        if (!shader.renderBatch(w, h, views.data(), n, px.data(), stats ? &st : nullptr)) {
+            std::fprintf(stderr, "--views failed: %s\n", shader.lastError().c_str());
+            return 1;
+        }
+        const double wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - b0).count();
+        std::printf("{\"views\": %d, \"w\": %d, \"h\": %d, \"scene\": \"%s\", \"format\": \"rgba8\", \"wall_ms\": %.3f", n, w,
+                    h, scene.c_str(), wall_ms);
+        if (stats) std::printf(", \"kernel_ms\": %.4f", st.kernel_ms);
+        std::printf("}\n");
+        for (int v = 0; v < n && !ppm.empty(); v++) {
+            char suffix[32];
+            std::snprintf(suffix, sizeof(suffix), ".%04d.ppm", v);
+            if (!write_ppm(ppm + suffix, px.data() + (size_t)v * w * h, w, h)) return 1;
+        }
+        return 0;
+    }
     sharded = sharded || gpus > 1;
     auto setAll = [&](const char* name, auto v) {
         for (rm::Shader* s : all) s->setUniform(name, v);
@@ -405,15 +480,7 @@ int main(int argc, char** argv) {
         } else if (!sharded ? !outputTexture.copyToHostRGBA8(shader, px) : !shardedTexture.copyToHostRGBA8(px)) {
             return 1;
         }
-        FILE* fp = std::fopen(ppm.c_str(), "wb");
-        if (!fp) return 1;
-        std::fprintf(fp, "P6\n%d %d\n255\n", w, h);
-        for (uint32_t v : px) {
-            unsigned char rgb[3] = {(unsigned char)(v & 255), (unsigned char)((v >> 8) & 255),
-                                    (unsigned char)((v >> 16) & 255)};
-            std::fwrite(rgb, 1, 3, fp);
-        }
-        std::fclose(fp);
+        if (!write_ppm(ppm, px.data(), w, h)) return 1;
     }
     return 0;
 }

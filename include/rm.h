@@ -490,6 +490,58 @@ rm_status rm_refine_rgba8(rm_ctx *ctx, int W, int H, const rm_aa_params *params,
 rm_status rm_render_aa_rgba8(rm_ctx *ctx, int W, int H, const rm_aa_params *params, uint32_t *out, uint8_t *mask,
                              rm_aa_stats *stats);
 
+/* View batches: n poses of the loaded scene rendered by one launch over views x
+ * tiles (no counterpart in the reference, whose frame loop draws one pose per
+ * frame).  View v's frame is at out + v * W * H elements --
+ * float4 for rm_render_batch, RGBA8 words for rm_render_batch_rgba8 -- tightly
+ * packed, row 0 first, and every byte of it is what rm_render / rm_render_rgba8
+ * writes after u_pos, u_mouse and u_time are set to the view's values; with a
+ * non-zero `offset`, what rm_render_accumulate[_rgba8] stores for
+ * u_sample_part = 1 and u_seed1 = offset + 0.5.  u_resolution (set or
+ * defaulted), rm_params.max_steps and shadow_max_steps are the context's, read
+ * at the call; the call neither reads nor changes the context's own u_pos,
+ * u_mouse, u_time or u_seed1.
+ *   `views` is a host pointer, read during the call (the caller may reuse it on
+ * return).  `out` is a device pointer (asynchronous on the ctx stream unless
+ * `stats` is given) or a host pointer (staged through the context's staging
+ * buffer; the call returns when the frames are written).  With `stats` the call
+ * waits and fills it: kernel_ms the one launch's time, pixels = n * W * H, scene
+ * the loaded scene, dispatch = RM_DISPATCH_ROW_MAJOR, everything else 0.  The
+ * counts behind rm_certified_steps / rm_reflection_cleared_steps are reset to
+ * 0, as by every render launch.
+ *   The batch always runs the timed kernels in one-wave 8x8 tiles, row-major
+ * per view.  These do not apply to it: rm_params.kernel, schedule and
+ * count_evals; rm_set_tile_order; step maps, accumulation into the target,
+ * bands, shards and the wire.
+ *   Size rule, checked before any pointer is used (rm_batch_bytes applies the
+ * same rule): W, H > 0; 0 <= n <= 65535; ceil(H / 8) <= 65535; n * W * H <= 2^31.
+ * rm_batch_bytes (host only, no GPU): the bytes of one view's frame and of the
+ * whole target (rgba8 != 0: RGBA8 words, else float4); either pointer may be
+ * NULL.
+ *   Errors: the size rule broken, `views` or `out` NULL with n > 0, or an
+ * offset component outside [-0.5, 0.5) or not finite: RM_ERR_INVALID_ARGUMENT;
+ * no scene: RM_ERR_NO_SCENE; a scene plugin: RM_ERR_SCENE ("view batches:
+ * built-in scenes only"), the target untouched; n = 0: RM_OK, nothing launched.
+ * The device copy of the per-view constants is a scratch buffer of the context
+ * (80 bytes per view for scenes S0 and T, 584 for O and OG) with the life and
+ * stream rule of rm_bloom's; several batches may be in flight on a stream at
+ * once.
+ *   Out of scope: scene plugins and per-view plugin uniforms; count_evals and
+ * step maps per view; an adaptive or costliest-first order across views; views
+ * of different sizes in one batch; device-resident view arrays; multi-GPU
+ * batches; adaptive supersampling of batched frames. */
+typedef struct rm_view {
+    float pos[3];    /* u_pos   */
+    float mouse[2];  /* u_mouse */
+    float time;      /* u_time  */
+    float offset[2]; /* sub-pixel offset of the fragment in pixels, each in [-0.5, 0.5); (0, 0): pixel centres.
+                        The fragment moves exactly as rm_render_accumulate moves it for u_seed1 = offset + 0.5 */
+} rm_view;
+rm_status rm_batch_bytes(int W, int H, int n, int rgba8, int64_t *frame_bytes, int64_t *total_bytes);
+rm_status rm_render_batch(rm_ctx *ctx, int W, int H, const rm_view *views, int n, float *out, rm_stats *stats);
+rm_status rm_render_batch_rgba8(rm_ctx *ctx, int W, int H, const rm_view *views, int n, uint32_t *out,
+                                rm_stats *stats);
+
 /* rm_render_band / rm_render_rows into RGBA8 rows (W uint32 per row). */
 rm_status rm_render_band_rgba8(rm_ctx *ctx, int W, int H, int band, int nshards, int shard, uint32_t *out,
                                rm_stats *stats);

@@ -130,6 +130,18 @@ public:
                                      reinterpret_cast<const float*>(directions), n, &params, rgba, rgba8,
                                      stats) == RM_OK;
     }
+    // rm.h rm_render_batch[_rgba8]: n views of the loaded scene from one launch
+    // (a turntable, an animation's frames, thumbnails, a stereo pair), view v's
+    // w x h frame at out + v * w * h elements, each what setUniform(u_pos,
+    // u_mouse, u_time) + RenderTexture::draw gives.  `views` is a host array;
+    // `out` a device pointer (asynchronous unless stats is given) or a host one.
+    // Built-in scenes only; the shader's own pose is neither read nor changed.
+    bool renderBatch(int w, int h, const rm_view* views, int n, std::uint32_t* out, rm_stats* stats = nullptr) {
+        return ctx_ && rm_render_batch_rgba8(ctx_, w, h, views, n, out, stats) == RM_OK;
+    }
+    bool renderBatch(int w, int h, const rm_view* views, int n, float* out, rm_stats* stats = nullptr) {
+        return ctx_ && rm_render_batch(ctx_, w, h, views, n, out, stats) == RM_OK;
+    }
 
 private:
     bool setArray(const char* name, int components, const float* v, std::size_t length) {

@@ -34,7 +34,8 @@ EXPORTS = ("rm_create", "rm_destroy", "rm_load_scene", "rm_set_uniform1f", "rm_s
            "rm_set_uniform4f", "rm_set_uniform1i", "rm_set_uniformfv", "rm_uniform_count", "rm_uniform_info_at",
            "rm_get_uniformfv", "rm_get_uniform1i", "rm_cast_rays", "rm_camera_rays",
            "rm_aa_offsets", "rm_aa_edge_mask", "rm_refine_rgba8", "rm_render_aa_rgba8", "rm_shade_rays", "rm_scene_eval_form",
-           "rm_resolution_cache_info", "rm_certified_steps", "rm_reflection_cleared_steps")
+           "rm_resolution_cache_info", "rm_certified_steps", "rm_reflection_cleared_steps",
+           "rm_batch_bytes", "rm_render_batch", "rm_render_batch_rgba8")
 
 # include/rm.h RM_ABI_VERSION: the struct layouts below
 ABI_VERSION = 3
@@ -94,6 +95,12 @@ class RmAaStats(ctypes.Structure):
     def as_dict(self):
         return dict(refined=int(self.refined), base_ms=float(self.base_ms), detect_ms=float(self.detect_ms),
                     refine_ms=float(self.refine_ms))
+
+
+class RmView(ctypes.Structure):
+    """include/rm.h rm_view: one view of a batch (rm_render_batch*)."""
+    _fields_ = [("pos", ctypes.c_float * 3), ("mouse", ctypes.c_float * 2), ("time", ctypes.c_float),
+                ("offset", ctypes.c_float * 2)]
 
 
 RAY_STATUS = {0: "miss", 1: "hit", 2: "exhausted"}  # include/rm.h RM_RAY_*
@@ -192,6 +199,9 @@ def lib() -> ctypes.CDLL:
         "rm_aa_edge_mask": ([c.c_int, c.c_int, c.c_int, vp, vp], c.c_int),
         "rm_refine_rgba8": ([vp, c.c_int, c.c_int, c.POINTER(RmAaParams), vp, vp, c.POINTER(RmAaStats)], c.c_int),
         "rm_render_aa_rgba8": ([vp, c.c_int, c.c_int, c.POINTER(RmAaParams), vp, vp, c.POINTER(RmAaStats)], c.c_int),
+        "rm_batch_bytes": ([c.c_int, c.c_int, c.c_int, c.c_int, c.POINTER(c.c_int64), c.POINTER(c.c_int64)], c.c_int),
+        "rm_render_batch": ([vp, c.c_int, c.c_int, vp, c.c_int, vp, c.POINTER(RmStats)], c.c_int),
+        "rm_render_batch_rgba8": ([vp, c.c_int, c.c_int, vp, c.c_int, vp, c.POINTER(RmStats)], c.c_int),
         "rm_shade_rays": ([vp, vp, c.c_int, vp, c.c_int64, c.POINTER(RmShadeParams), vp, vp, c.POINTER(RmStats)],
                           c.c_int),
         "rm_sharded_layout": ([c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.POINTER(RmShardLayout)], c.c_int),

@@ -655,6 +655,36 @@ class Renderer:
               self._ctx)
         return (out, self._stats(s)) if stats else out
 
+    # --- view batches (rm_render_batch, rm_render_batch_rgba8) -------------
+    def render_batch(self, W: int, H: int, views, out=None, rgba8: bool = True, stats: bool = False):
+        """n views of the loaded scene from one launch (rm_render_batch[_rgba8];
+        DESIGN.md 2.26).  views: anything pack_views takes -- a sequence of
+        dicts in POSES' form (pos, mouse, time) with an optional `offset`
+        (sub-pixel, each component in [-0.5, 0.5)), or an (n, 6) / (n, 8)
+        float32 array or tensor of rows px py pz mx my t [ox oy].  A CUDA
+        tensor of views is copied to the host first, which synchronises.
+        Returns [n, H, W] int32 RGBA8 words (rgba8=True) or [n, H, W, 4]
+        float32, view v's frame byte for byte what set_pose + render_rgba8 /
+        render gives; `out`: a device tensor of that many elements (allocated
+        if None; asynchronous on the renderer's stream unless stats=True) or a
+        numpy array (staged).  u_resolution, max_steps and shadow_max_steps
+        are the renderer's; its own pose is neither read nor changed.  The
+        timed kernels in row-major one-wave tiles, always: kernel, schedule,
+        count_evals and set_tile_order do not apply.  Built-in scenes only."""
+        v = pack_views(views)
+        n = len(v)
+        per_px = 1 if rgba8 else 4
+        if out is None:
+            torch = _torch()
+            out = torch.empty((n, H, W) if rgba8 else (n, H, W, 4), dtype=torch.int32 if rgba8 else torch.float32,
+                              device=f"cuda:{self.device}")
+        _check_out(out, n * H * W * per_px)
+        s = RmStats()
+        fn = lib().rm_render_batch_rgba8 if rgba8 else lib().rm_render_batch
+        check(fn(self._ctx, int(W), int(H), ctypes.c_void_p(v.ctypes.data), n, self._ptr(out),
+                 ctypes.byref(s) if stats else None), self._ctx)
+        return (out, self._stats(s)) if stats else out
+
     # --- adaptive supersampling (rm_render_aa_rgba8, rm_refine_rgba8) -----
     def _aa(self, fn, W, H, samples, threshold, frame8, mask, stats):
         """frame8: [H, W] RGBA8 words, a device tensor or a numpy array (staged);
@@ -694,6 +724,44 @@ class Renderer:
         place; returns as render_aa does."""
         H, W = frame8.shape
         return self._aa(lib().rm_refine_rgba8, W, H, samples, threshold, frame8, mask, stats)
+
+
+def pack_views(views):
+    """The views of Renderer.render_batch as the contiguous float32 [n, 8]
+    array rm_render_batch reads (rm.h rm_view: px py pz mx my t ox oy).  No
+    GPU, no librm.  views: a sequence of dicts in POSES' form -- pos (3),
+    mouse (2), time, and optionally offset (2; default (0, 0), the pixel
+    centres) -- or an (n, 6) array or tensor (offsets 0) or an (n, 8) one.  A
+    CUDA tensor is copied to the host (which synchronises).  An empty sequence
+    gives [0, 8].  ValueError: another shape, a value that is not finite, or an
+    offset component outside [-0.5, 0.5)."""
+    import numpy as np
+    if hasattr(views, "detach"):  # a torch tensor
+        views = views.detach().cpu().numpy()
+    if isinstance(views, np.ndarray):
+        a = np.asarray(views, np.float32)
+        if a.ndim != 2 or a.shape[1] not in (6, 8):
+            raise ValueError(f"pack_views: an (n, 6) or (n, 8) array, not {tuple(a.shape)}")
+    else:
+        rows = []
+        for i, v in enumerate(views):
+            if not hasattr(v, "keys"):
+                raise ValueError(f"pack_views: view {i} is not a dict (pos, mouse, time[, offset])")
+            extra = set(v.keys()) - {"pos", "mouse", "time", "offset"}
+            if extra or not {"pos", "mouse", "time"} <= set(v.keys()):
+                raise ValueError(f"pack_views: view {i} needs pos, mouse, time and optionally offset")
+            pos, mouse, off = tuple(v["pos"]), tuple(v["mouse"]), tuple(v.get("offset", (0.0, 0.0)))
+            if (len(pos), len(mouse), len(off)) != (3, 2, 2):
+                raise ValueError(f"pack_views: view {i}: pos has 3 components, mouse and offset 2")
+            rows.append(pos + mouse + (float(v["time"]),) + off)
+        a = np.asarray(rows, np.float32).reshape(len(rows), 8)
+    out = np.zeros((a.shape[0], 8), np.float32)
+    out[:, :a.shape[1]] = a
+    if not np.isfinite(out).all():
+        raise ValueError("pack_views: a value is not finite")
+    if ((out[:, 6:] < np.float32(-0.5)) | (out[:, 6:] >= np.float32(0.5))).any():
+        raise ValueError("pack_views: an offset component is outside [-0.5, 0.5)")
+    return out
 
 
 def aa_offsets(samples: int):

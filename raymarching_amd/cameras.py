@@ -77,6 +77,41 @@ def cubemap_rays(size: int, face) -> np.ndarray:
     return np.ascontiguousarray(d, F32)
 
 
+SPONGE_CENTRE = (0.0, 3.0, 0.0)  # the sponge of scenes T and O (transformR's translation, common.frag:434-441)
+
+
+def turntable(n: int, radius: float, height: float, target_time=None) -> list:
+    """n views for Renderer.render_batch on a circle of `radius` at y =
+    `height` around the sponge at (0, 3, 0), each looking at its centre: a list
+    of dicts in POSES' form (pos, mouse, time), values rounded to float32.
+    target_time: the u_time of every view (the sponge's own rotation is
+    2 * u_time degrees); None: 0.
+
+    View k stands at the angle phi = 2 pi k / n: pos = (radius sin phi, height,
+    radius cos phi), so view 0 is on the +Z side looking down -Z, as main()'s
+    camera does before the mouse rotations.  camera_ray turns the forward ray
+    (0, 0, -1) by rd.yz *= rot(-u_mouse.y), then rd.xz *= rot(u_mouse.x), with
+    rot(a) = mat2(cos a, -sin a, sin a, cos a) applied to a row vector
+    (output_shader.frag:403-404), which gives
+        forward = (cos my sin mx, -sin my, -cos my cos mx).
+    The direction to the centre is (-radius sin phi, 3 - height, -radius cos phi)
+    / L with L = sqrt(radius^2 + (3 - height)^2); equating the two,
+        yaw   u_mouse.x = -phi  (wrapped into (-pi, pi]),
+        pitch u_mouse.y = atan2(height - 3, radius)  (positive: looking down).
+    """
+    if n < 0 or not radius > 0.0:
+        raise ValueError("turntable: n >= 0 and radius > 0")
+    pitch = float(F32(np.arctan2(float(height) - SPONGE_CENTRE[1], float(radius))))
+    t = float(F32(0.0 if target_time is None else target_time))
+    views = []
+    for k in range(int(n)):
+        phi = 2.0 * np.pi * k / n
+        yaw = (-phi if phi < np.pi else 2.0 * np.pi - phi) + 0.0  # (+ 0.0: view 0's yaw is 0, not -0)
+        pos = (float(F32(radius * np.sin(phi))), float(F32(height)), float(F32(radius * np.cos(phi))))
+        views.append(dict(pos=pos, mouse=(float(F32(yaw)), pitch), time=t))
+    return views
+
+
 def equirect_rays(W: int, H: int) -> np.ndarray:
     """An equirectangular panorama: longitude -pi..pi along a row (the centre
     column looks down -Z, +X to its right), latitude +pi/2 (up, +Y) at the top

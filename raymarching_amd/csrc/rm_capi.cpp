@@ -104,6 +104,12 @@ rm_status rm_destroy(rm_ctx *ctx) {
     if (ctx->aa_queue) (void)hipFree(ctx->aa_queue);
     if (ctx->aa_ev) (void)hipEventDestroy(ctx->aa_ev);
     if (ctx->aa_ev2) (void)hipEventDestroy(ctx->aa_ev2);
+    if (ctx->batch_views) (void)hipFree(ctx->batch_views);
+    if (ctx->batch_ev) (void)hipEventDestroy(ctx->batch_ev);
+    for (auto &b : ctx->batch_slot) {  // (wait_idle above: no upload still reads a block)
+        if (b.host) (void)hipHostFree(b.host);
+        if (b.copied) (void)hipEventDestroy(b.copied);
+    }
     if (ctx->tile_order) (void)hipFree(ctx->tile_order);
     for (rm_ctx::Sched &e : ctx->sched) (void)sched_release(ctx, e);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);

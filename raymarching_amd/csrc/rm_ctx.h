@@ -85,6 +85,27 @@ struct rm_ctx {
     hipStream_t aa_stream = nullptr;
     bool aa_pending = false;
     hipEvent_t aa_ev2 = nullptr;  // a third timing event (rm_aa_stats: detect | refine), made on first use
+    // view batches (rm_batch_host.cpp): the device copy of a batch's per-view records (rm_batch.h ViewConst), one
+    // buffer per context, grown on demand, with bloom's stream rule -- batch_ev is recorded when the context
+    // leaves the stream of its last batch, and a batch on another stream first waits for it
+    void *batch_views = nullptr;
+    size_t batch_bytes = 0;
+    hipEvent_t batch_ev = nullptr;
+    hipStream_t batch_stream = nullptr;
+    bool batch_pending = false;
+    // ... and the host side of their upload: pinned blocks taken in turn, each with the event recorded after its
+    // asynchronous copy.  A call fills a block only once that event has completed, so a batch enqueued while the
+    // one before it still runs never overwrites records a copy has yet to read (at most kBatchSlots uploads in
+    // flight; the next call waits for the oldest copy, not for its kernel's frames)
+    struct BatchSlot {
+        void *host = nullptr;
+        size_t bytes = 0;
+        hipEvent_t copied = nullptr;
+        bool used = false;  // `copied` has been recorded
+    };
+    static constexpr int kBatchSlots = 4;
+    BatchSlot batch_slot[kBatchSlots];
+    int batch_next = 0;
     // FrameConst.rcp_* of scenes S0/T (rm_render_host.cpp frame_rcp): the device's reciprocals of the frame
     // size and of u_resolution.y, kept per resolution -- the key changes when a window is resized, not per frame
     // (u_time and the pose do not enter it).  A small fixed-size cache, least recently used out, so that callers
@@ -194,6 +215,11 @@ void wait_idle(rm_ctx *ctx);                       // rm_destroy: nothing the co
 
 // ---- rm_render_host.cpp
 int pick_kernel(const rm_params &p);
+// the pose-dependent members of F (position, camera and sponge rotations, camq_*, time, mouse): frame_const's own
+// code, which a view batch calls once per view (rm_batch_host.cpp)
+void pose_const(rm::FrameConst &F, const float pos[3], const float mouse[2], float time);
+float seed_jitter(float seed);  // fract(seed) - 0.5: FrameConst.jit_* of u_seed1
+rm_status ensure_staging(rm_ctx *ctx, size_t bytes);  // ctx->staging holds at least `bytes`
 rm::FrameConst frame_const(const rm_ctx *c, int W, int H, const rm::RowPart &part, int nrows);
 // F.rcp_* for F's W, H and res_y (scenes S0/T; every launch whose kernel builds camera rays calls it after
 // frame_const, which leaves them 0): from the context's per-resolution cache, computed on the device on a miss

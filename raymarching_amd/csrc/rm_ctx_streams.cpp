@@ -197,6 +197,13 @@ rm_status set_stream(rm_ctx *ctx, hipStream_t s) {
         RM_HIP(hipEventRecord(ctx->aa_ev, ctx->stream));
         ctx->aa_pending = false;
     }
+    if (s != ctx->stream && ctx->batch_pending && ctx->batch_stream == ctx->stream) {
+        // the same for the last view batch's records (rm_batch_host.cpp batch_scratch)
+        RM_HIP(hipSetDevice(ctx->device));
+        if (!ctx->batch_ev) RM_HIP(hipEventCreateWithFlags(&ctx->batch_ev, hipEventDisableTiming));
+        RM_HIP(hipEventRecord(ctx->batch_ev, ctx->stream));
+        ctx->batch_pending = false;
+    }
 #ifdef RM_ANALYSIS_LEAVE_NO_RECORD
     // analysis builds only (-DRM_ANALYSIS_LEAVE_NO_RECORD, tools/scale_model.py
     // prices the marker with it; unsafe: a later release of a schedule buffer or

@@ -81,6 +81,8 @@ constexpr uint64_t kSchedPeriod = 16;
 // 2.6).
 constexpr int kSchedDilate = 2;
 
+}  // namespace
+
 rm_status ensure_staging(rm_ctx *ctx, size_t bytes) {
     if (ctx->staging_bytes >= bytes) return RM_OK;
     if (ctx->staging) (void)hipFree(ctx->staging);
@@ -91,8 +93,6 @@ rm_status ensure_staging(rm_ctx *ctx, size_t bytes) {
     return RM_OK;
 }
 
-}  // namespace
-
 // rm_params.kernel: 0 auto, 1 = 16x16-pixel workgroups, 2 = 8x8-pixel workgroups
 int pick_kernel(const rm_params &p) {
     if (p.kernel == 1) return rm::KERNEL_TILE16;
@@ -101,29 +101,40 @@ int pick_kernel(const rm_params &p) {
     return rm::KERNEL_TILE8;  // 0 auto, 2: measured fastest on every config
 }
 
+// The members of F that depend on the pose (u_pos, u_mouse, u_time) and nothing
+// else: frame_const below calls it with the context's pose, a view batch
+// (rm_batch_host.cpp) once per view with the view's -- one body under this
+// file's -ffp-contract=off, so the two paths cannot round differently.
+void pose_const(FrameConst &F, const float pos[3], const float mouse[2], float time) {
+    F.pos_x = pos[0]; F.pos_y = pos[1]; F.pos_z = pos[2];
+    // rot(a) = mat2(cos a, -sin a, sin a, cos a) (common.frag:1088-1092)
+    float a1 = -mouse[1], a2 = mouse[0];
+    F.cam1_c = rm::glsl_cos(a1); F.cam1_s = rm::glsl_sin(a1);
+    F.cam2_c = rm::glsl_cos(a2); F.cam2_s = rm::glsl_sin(a2);
+    // transformR(.., vec3(180, u_time * 2, 0)): rotationY(-rot.y), rotationX(-rot.x)
+    // with radians(x) = x * pi/180 (common.frag:190-214,434-441)
+    float rot_y = time * 2.0f, rot_x = 180.0f;
+    float ay = -rot_y * 0.017453292519943295f, ax = -rot_x * 0.017453292519943295f;
+    F.ry_c = rm::glsl_cos(ay); F.ry_s = rm::glsl_sin(ay);
+    F.rx_c = rm::glsl_cos(ax); F.rx_s = rm::glsl_sin(ax);
+    rm::camera_sponge_origin(F);  // (after pos and the sponge rotation)
+    F.time = time;
+    F.mouse_x = mouse[0];
+    F.mouse_y = mouse[1];
+}
+
+// fract(u_seed1) - 0.5 (GLSL fract, x - floor(x)): rm_render_accumulate*'s sub-pixel offset of the fragment
+float seed_jitter(float seed) { return (seed - std::floor(seed)) - 0.5f; }
+
 FrameConst frame_const(const rm_ctx *c, int W, int H, const RowPart &part, int nrows) {
     FrameConst F;
     std::memset(&F, 0, sizeof(F));
     F.res_x = c->res_set ? c->res[0] : (float)W;
     F.res_y = c->res_set ? c->res[1] : (float)H;
-    F.pos_x = c->pos[0]; F.pos_y = c->pos[1]; F.pos_z = c->pos[2];
-    // rot(a) = mat2(cos a, -sin a, sin a, cos a) (common.frag:1088-1092)
-    float a1 = -c->mouse[1], a2 = c->mouse[0];
-    F.cam1_c = rm::glsl_cos(a1); F.cam1_s = rm::glsl_sin(a1);
-    F.cam2_c = rm::glsl_cos(a2); F.cam2_s = rm::glsl_sin(a2);
-    // transformR(.., vec3(180, u_time * 2, 0)): rotationY(-rot.y), rotationX(-rot.x)
-    // with radians(x) = x * pi/180 (common.frag:190-214,434-441)
-    float rot_y = c->time * 2.0f, rot_x = 180.0f;
-    float ay = -rot_y * 0.017453292519943295f, ax = -rot_x * 0.017453292519943295f;
-    F.ry_c = rm::glsl_cos(ay); F.ry_s = rm::glsl_sin(ay);
-    F.rx_c = rm::glsl_cos(ax); F.rx_s = rm::glsl_sin(ax);
-    rm::camera_sponge_origin(F);  // (after pos and the sponge rotation)
+    pose_const(F, c->pos, c->mouse, c->time);
     F.W = W; F.H = H;
     F.cycle = part.cycle; F.offset = part.offset; F.run = part.run; F.nrows = nrows;
     F.run_magic = rm::div_magic((uint32_t)part.run, (uint64_t)H + 1);  // packed rows j < H
-    F.time = c->time;
-    F.mouse_x = c->mouse[0];
-    F.mouse_y = c->mouse[1];
     F.max_steps = c->params.max_steps;
     // 0 (unbounded, the reference) travels as INT_MAX: one compare per shadow step
     F.shadow_max_steps = c->params.shadow_max_steps > 0 ? c->params.shadow_max_steps : 0x7fffffff;
@@ -179,8 +190,8 @@ rm_status render_dev(rm_ctx *ctx, int W, int H, const RowPart &part, int row0, i
     if (accum) {  // fract(u_seed1) - 0.5 (GLSL fract, x - floor(x)), per frame
         F.accumulate = 1;
         F.sample_part = ctx->sample_part;
-        F.jit_x = (ctx->seed1[0] - std::floor(ctx->seed1[0])) - 0.5f;
-        F.jit_y = (ctx->seed1[1] - std::floor(ctx->seed1[1])) - 0.5f;
+        F.jit_x = seed_jitter(ctx->seed1[0]);
+        F.jit_y = seed_jitter(ctx->seed1[1]);
     }
     rm_ctx::Sched *sc = nullptr;
     if (ctx->tile_order) {  // an explicit order wins
