@@ -637,6 +637,18 @@ rm_status rm_certified_steps(rm_ctx *ctx, uint64_t *steps);
  * other scene and for uncounted renders.  A call of its own, as rm_certified_steps: rm_stats keeps its layout. */
 rm_status rm_reflection_cleared_steps(rm_ctx *ctx, uint64_t *steps);
 
+/* The ray-steps scene T's near-sky ladder proves away, of this context's last render launch (counted and reset as
+ * rm_certified_steps' count is): of its `evals`, and none of them in its `skipped` or in the two counts above, the
+ * primary-march steps, and the reflection-march steps begun at a depth < 3, of the waves whose 64 rays all miss
+ * the sponge's cube inflated by the margin m that max_steps admits (csrc/rm_far_sky.h, DESIGN.md 2.27: m = 0.25
+ * from 39 steps, 0.1 from 63, 0.05 from 98, 0.02 from 205) and end 3.1 beyond it, but do not all miss the cube
+ * inflated by 0.25 with max_steps >= 208 -- those waves' steps are in `skipped`, as before.  Each such march is
+ * proved to return ZFAR, and the reflection factor 1, and the uninstrumented kernels take neither.  0 under a
+ * step cap below 39, for every other scene and for uncounted renders.  The uninstrumented kernels execute
+ * evals - skipped - certified - reflection_cleared - near_sky steps.  A call of its own, as rm_certified_steps:
+ * rm_stats keeps its layout and RM_ABI_VERSION its value. */
+rm_status rm_near_sky_steps(rm_ctx *ctx, uint64_t *steps);
+
 /* The render kernels' code objects by content (16 hex digits of a SHA-256 of
  * the translation units that hold them): rocprofv3 counters of a render launch
  * (profiles/pmc_counters.json) name the build they counted, and bench.py

@@ -35,6 +35,7 @@ EXPORTS = ("rm_create", "rm_destroy", "rm_load_scene", "rm_set_uniform1f", "rm_s
            "rm_get_uniformfv", "rm_get_uniform1i", "rm_cast_rays", "rm_camera_rays",
            "rm_aa_offsets", "rm_aa_edge_mask", "rm_refine_rgba8", "rm_render_aa_rgba8", "rm_shade_rays", "rm_scene_eval_form",
            "rm_resolution_cache_info", "rm_certified_steps", "rm_reflection_cleared_steps",
+           "rm_near_sky_steps",
            "rm_batch_bytes", "rm_render_batch", "rm_render_batch_rgba8")
 
 # include/rm.h RM_ABI_VERSION: the struct layouts below
@@ -219,6 +220,7 @@ def lib() -> ctypes.CDLL:
         "rm_resolution_cache_info": ([vp, c.POINTER(c.c_int), c.POINTER(c.c_int)], c.c_int),
         "rm_certified_steps": ([vp, c.POINTER(c.c_uint64)], c.c_int),
         "rm_reflection_cleared_steps": ([vp, c.POINTER(c.c_uint64)], c.c_int),
+        "rm_near_sky_steps": ([vp, c.POINTER(c.c_uint64)], c.c_int),
         "rm_cycle_rows": ([c.c_int, c.c_int, c.c_int, c.c_int, c.POINTER(c.c_int)], c.c_int),
         "rm_render_cycle_rows": ([vp, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, vp,
                                   c.POINTER(RmStats)], c.c_int),

@@ -203,11 +203,19 @@ class Renderer:
         check(lib().rm_reflection_cleared_steps(self._ctx, ctypes.byref(n)), self._ctx)
         return int(n.value)
 
+    def near_sky_steps(self) -> int:
+        """rm_near_sky_steps: of the last counted render's evals, the primary- and reflection-march ray-steps of
+        scene T's waves that the near-sky ladder lets skip both marches; 0 elsewhere."""
+        n = ctypes.c_uint64(0)
+        check(lib().rm_near_sky_steps(self._ctx, ctypes.byref(n)), self._ctx)
+        return int(n.value)
+
     def _stats(self, s) -> dict:
-        """rm_stats as a dict, with `certified` (rm_certified_steps of the same call) and `reflection_cleared`
-        (rm_reflection_cleared_steps): every stats dict
+        """rm_stats as a dict, with `certified` (rm_certified_steps of the same call), `reflection_cleared`
+        (rm_reflection_cleared_steps) and `near_sky` (rm_near_sky_steps): every stats dict
         made from an rm_stats carries the key (render_aa's is an rm_aa_stats: other members, no ray-step counts)"""
-        return dict(s.as_dict(), certified=self.certified_steps(), reflection_cleared=self.reflection_cleared_steps())
+        return dict(s.as_dict(), certified=self.certified_steps(), reflection_cleared=self.reflection_cleared_steps(),
+                    near_sky=self.near_sky_steps())
 
     def render(self, W: int, H: int, out=None, stats: bool = False):
         """Full frame into `out` (device tensor [H,W,4] f32; allocated if None)."""

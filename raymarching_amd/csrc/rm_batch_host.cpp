@@ -76,6 +76,7 @@ rm_status batch_dev(rm_ctx *ctx, int W, int H, const rm_view *views, int n, void
         V.jit_y = seed_jitter(views[v].offset[1] + 0.5f);
         rm::batch_record_write(ctx->scene, slot->host, v, V);
     }
+    F.near_r = V.near_r;  // (shared by the views: pose_const withdraws the ladder's radius if any view's pose asks it)
     if (rm_status st = batch_scratch(ctx, bytes)) return st;
     void *rec_d = ctx->batch_views;
     RM_HIP(hipMemcpyAsync(rec_d, slot->host, bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -87,6 +88,7 @@ rm_status batch_dev(rm_ctx *ctx, int W, int H, const rm_view *views, int n, void
 
     ctx->last_certified = 0;  // (of the last render launch alone; this one counts nothing)
     ctx->last_refl_cleared = 0;
+    ctx->last_near_sky = 0;
     if (stats) RM_HIP(hipEventRecord(ctx->ev0, ctx->stream));
     const hipError_t e = ctx->scene == rm::SCENE_S0 || ctx->scene == rm::SCENE_T
                              ? rm::launch_batch_t(ctx->scene, F, rec_d, n, out, rgba8, ctx->stream)

@@ -74,7 +74,7 @@ rm_status rm_create(rm_ctx **out, int device) {
     rm_ctx *ctx = new rm_ctx();
     ctx->device = device;
     hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipMalloc(&ctx->d_evals, 5 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMalloc(&ctx->d_evals, 6 * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipEventCreate(&ctx->ev0);
     if (e == hipSuccess) e = hipEventCreate(&ctx->ev1);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->done, hipEventDisableTiming);
@@ -861,6 +861,12 @@ rm_status rm_certified_steps(rm_ctx *ctx, uint64_t *steps) {
 rm_status rm_reflection_cleared_steps(rm_ctx *ctx, uint64_t *steps) {
     if (!ctx || !steps) return RM_ERR_INVALID_ARGUMENT;
     *steps = ctx->last_refl_cleared;
+    return RM_OK;
+}
+
+rm_status rm_near_sky_steps(rm_ctx *ctx, uint64_t *steps) {
+    if (!ctx || !steps) return RM_ERR_INVALID_ARGUMENT;
+    *steps = ctx->last_near_sky;
     return RM_OK;
 }
 

@@ -60,6 +60,7 @@ struct rm_ctx {
     std::set<std::string> warned;
     unsigned long long *d_evals = nullptr;
     unsigned long long last_certified = 0;  // rm_certified_steps(): d_evals[3] of the last render launch, 0 unless it was counted and filled an rm_stats
+    unsigned long long last_near_sky = 0;  // rm_near_sky_steps(): d_evals[5] of the last render launch, as last_certified
     unsigned long long last_refl_cleared = 0;  // rm_reflection_cleared_steps(): d_evals[4] of the last render launch, as last_certified
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float4 *staging = nullptr;
@@ -216,7 +217,8 @@ void wait_idle(rm_ctx *ctx);                       // rm_destroy: nothing the co
 // ---- rm_render_host.cpp
 int pick_kernel(const rm_params &p);
 // the pose-dependent members of F (position, camera and sponge rotations, camq_*, time, mouse): frame_const's own
-// code, which a view batch calls once per view (rm_batch_host.cpp)
+// code, which a view batch calls once per view (rm_batch_host.cpp).  It also takes F.near_r back to the far-sky
+// cube's radius under a pose whose rotations do not keep a direction's length (rm_far_sky.h 3.)
 void pose_const(rm::FrameConst &F, const float pos[3], const float mouse[2], float time);
 float seed_jitter(float seed);  // fract(seed) - 0.5: FrameConst.jit_* of u_seed1
 rm_status ensure_staging(rm_ctx *ctx, size_t bytes);  // ctx->staging holds at least `bytes`

@@ -72,8 +72,9 @@ struct FrameConst {
     uint32_t gx_magic;             // floor(t / tiles_x) = umulhi(t, gx_magic) for every tile t, or 0: divide
     float camq_x, camq_y, camq_z;  // sponge_space<false>(u_pos): the primary rays' origin in sponge space (scene T),
                                    // the same FMAs in the same order on the host (camera_sponge_origin)
-    int far_sky;                   // scene T with max_steps >= rmfs::kFarSkyN0: waves whose rays all pass
-                                   // rmfs::far_sky_ray skip the primary and the reflection march (rm_far_sky.h;
+    int far_sky;                   // scene T with max_steps >= rmfs::kFarSkyN0: the instrumented kernels count the
+                                   // primary and reflection marches of waves whose rays all pass rmfs::far_sky_ray
+                                   // in rm_stats.skipped (rm_far_sky.h; the timed kernels' vote is near_r below;
                                    // in the struct's tail padding: no other member moves)
     // (the members below are new at the struct's end: nothing before them moves)
     float rcp_w, rcp_h, rcp_res_y;  // scenes S0/T (camera_ray<FAST>): v_rcp_f32 of (float)W, (float)H and res_y,
@@ -83,6 +84,10 @@ struct FrameConst {
                                     // 2 every wave's rows lie in one run (render_tile_at finds the run once per
                                     // wave, shard_row_of_wave); 0 (a band of 3, ragged parts, a part starting
                                     // inside a wave's rows): each lane divides
+    float near_r;                   // scene T: the timed kernels' far-sky vote tests the cube of this half-size, the
+                                    // smallest rung of rmfs::kNearSkyLadder that max_steps admits
+                                    // (rmfs::near_sky_radius), or 0: no wave skips its marches.
+                                    // far_sky above stays the instrumented kernels' (rm_stats.skipped)
 };
 static_assert(rmfs::kFarSkyDepth == ZFAR, "rm_far_sky.h restates ZFAR");
 static_assert(rmrc::kNear == ZNEAR, "rm_refl_clear.h restates ZNEAR");
@@ -281,6 +286,8 @@ struct Tally {
                              // rmsc::shadow_clear, which the timed kernels leave out (scene T)
     uint32_t refl_cleared = 0;  // of evals, none of them in skipped or certified: the reflection-march steps of
                                 // hit lanes that pass rmrc::refl_clear, which the timed kernels leave out (scene T)
+    uint32_t near_sky = 0;  // of evals, none of them in the three above: the primary- and reflection-march steps of
+                            // waves that pass the vote at FrameConst.near_r but not the far-sky vote (scene T)
 };
 constexpr uint32_t FL_SPHERE = 9;      // sphere(): sub 3, dot 5, sub 1 (+ sqrt)
 constexpr uint32_t FL_TRANSFORM = 18;  // p - (0,3,0): 3; transformR's 3x3 rotation: 15

@@ -25,7 +25,7 @@ rm_status cast_dev(rm_ctx *ctx, rm::RayQuery Q, int inside, rm_stats *stats) {
     const FrameConst F = frame_const(ctx, 1, 1, RowPart{1, 0, 1}, 1);
     if (stats) {
         Q.evals = ctx->d_evals;
-        RM_HIP(hipMemsetAsync(ctx->d_evals, 0, 5 * sizeof(unsigned long long), ctx->stream));
+        RM_HIP(hipMemsetAsync(ctx->d_evals, 0, 6 * sizeof(unsigned long long), ctx->stream));
         RM_HIP(hipEventRecord(ctx->ev0, ctx->stream));
     }
     const hipError_t e =
@@ -45,6 +45,7 @@ rm_status cast_dev(rm_ctx *ctx, rm::RayQuery Q, int inside, rm_stats *stats) {
         stats->evals = ev;
         ctx->last_certified = 0;  // (rm_certified_steps: a ray query certifies nothing)
         ctx->last_refl_cleared = 0;
+        ctx->last_near_sky = 0;
         stats->pixels = (uint64_t)Q.n;
         stats->kernel_ms = ms;
         stats->scene = ctx->scene;

@@ -673,17 +673,37 @@ __device__ __forceinline__ V3 render_T_from(const FrameConst& F, const LinRay& p
     // far_sky_ray the primary march returns ZFAR and the reflection factor is 1, on every lane, whatever their
     // steps.  Decided per wave (a scalar branch: a mixed wave marches as before), with RSTOP's modes: 1 (timed
     // kernels) takes neither march, 2 (instrumented) takes both and counts all their steps in cnt.skipped.
-    bool far = false;
+    // The near-sky ladder (rm_far_sky.h 3.): the timed kernels take the same vote against the cube
+    // of half-size F.near_r, the smallest the launch's step cap admits (the host's choice; never larger than
+    // kFarSkyR where F.far_sky is set, and the test is monotonic in r: a far-sky wave passes it).  The instrumented
+    // kernels keep cnt.skipped to the far-sky vote and count the marches of the waves that pass the new vote alone
+    // in cnt.near_sky, less the reflection steps that cast_ray_T's RS = 2 already put into cnt.skipped.
+    bool far = false, vote = false;
     if constexpr (P::kFarSky && RSTOP != 0) {
-        if (F.far_sky)
-            far = __builtin_amdgcn_ballot_w64(
-                      rmfs::far_sky_ray(prim.o.x, prim.o.y, prim.o.z, prim.d.x, prim.d.y, prim.d.z)) ==
+        if (F.near_r > 0.0f) {
+            float r = F.near_r;
+            asm volatile("" : "+v"(r));  // (once per wave: an SGPR here and the literal 2^-100 do not fit one FMA)
+            vote = __builtin_amdgcn_ballot_w64(
+                      rmfs::near_sky_ray(prim.o.x, prim.o.y, prim.o.z, prim.d.x, prim.d.y, prim.d.z, r)) ==
                   __builtin_amdgcn_ballot_w64(true);  // (every active lane)
+        }
+        if constexpr (RSTOP == 2) {
+            if (F.far_sky)
+                far = __builtin_amdgcn_ballot_w64(
+                          rmfs::far_sky_ray(prim.o.x, prim.o.y, prim.o.z, prim.d.x, prim.d.y, prim.d.z)) ==
+                      __builtin_amdgcn_ballot_w64(true);
+        } else {
+            far = vote;
+        }
     }
+    const bool near = RSTOP == 2 && vote && !far;
     const uint32_t e0 = cnt.evals;
     float depth = ZFAR;
     if (RSTOP != 1 || !far) depth = cast_ray_T<NB>(F, prim, cnt);
-    if constexpr (RSTOP == 2) cnt.skipped += far ? cnt.evals - e0 : 0u;
+    if constexpr (RSTOP == 2) {
+        cnt.skipped += far ? cnt.evals - e0 : 0u;
+        cnt.near_sky += near ? cnt.evals - e0 : 0u;
+    }
     V3 p = ro + rd * depth;
     // (the timed kernels' far-sky waves: the normal's and the AO's probes as box terms, normal_fast's BOX)
     const bool boxp = RSTOP == 1 && far;
@@ -719,6 +739,8 @@ __device__ __forceinline__ V3 render_T_from(const FrameConst& F, const LinRay& p
                 Tally none;
                 const bool phit = menger_at<NB>(prim, depth, none) < 0.001f;
                 cnt.refl_cleared += rclear && phit ? (cnt.evals - e1) - (cnt.skipped - s1) : 0u;
+                // (a near-sky wave's lanes all end at ZFAR, where phit is false: the two never overlap)
+                cnt.near_sky += near ? (cnt.evals - e1) - (cnt.skipped - s1) : 0u;
             }
             // |pr - p| >= 0.01 (the offset of ror; the march adds depth >= ZNEAR along rdir): far above 2^-96, below
             // which alone sqrtf's rescaling acts, so the bare v_sqrt_f32 is length()'s float (apply_scattering, TRIM)
@@ -930,18 +952,19 @@ __device__ __forceinline__ uint32_t tile_clocks(uint64_t t_start) {
     return dt > 0xffffffffull ? 0xffffffffu : (uint32_t)dt;
 }
 // instrumented launches: pixel (x, packed row j)'s ray-steps into the step map,
-// the wave's tallies into evals[0..4]
+// the wave's tallies into evals[0..5]
 __device__ __forceinline__ void store_tally(const FrameConst& F, unsigned long long* evals, const Tally& cnt, int x,
                                             int j, int lane) {
     if (F.evals_map && x < F.W && j < F.nrows) F.evals_map[(size_t)j * F.W + x] = cnt.evals;
     uint32_t se = wave_sum_u32(cnt.evals), sf = wave_sum_u32(cnt.flop), ss = wave_sum_u32(cnt.skipped);
-    uint32_t sc = wave_sum_u32(cnt.certified), sr = wave_sum_u32(cnt.refl_cleared);
+    uint32_t sc = wave_sum_u32(cnt.certified), sr = wave_sum_u32(cnt.refl_cleared), sn = wave_sum_u32(cnt.near_sky);
     if (lane == 0) {
         atomicAdd(&evals[0], (unsigned long long)se);
         atomicAdd(&evals[1], (unsigned long long)sf);
         if (ss) atomicAdd(&evals[2], (unsigned long long)ss);
         if (sc) atomicAdd(&evals[3], (unsigned long long)sc);
         if (sr) atomicAdd(&evals[4], (unsigned long long)sr);
+        if (sn) atomicAdd(&evals[5], (unsigned long long)sn);
     }
 }
 
@@ -1010,7 +1033,8 @@ template <> struct Tiling<KERNEL_PERSIST> : Tiling<KERNEL_TILE8> {};
 // OUT = float4 (gl_FragColor) or uint32_t (RGBA8, packed in the epilogue, so
 // the displayed frame costs 4 B/px of HBM instead of 16 + 20 for a pack
 // pass).  COUNT: instrumented build, ray-steps and FLOP summed per wave into
-// evals[0..4] (ray-steps, FLOP, ray-steps the timed kernels skip by an early exit, by the shadow certificate, and by the reflection certificate).
+// evals[0..5] (ray-steps, FLOP, ray-steps the timed kernels skip by an early exit, by the shadow certificate, by
+// the reflection certificate, and by the near-sky ladder).
 // (bx, by): the tile's position in dispatch order on a gx-wide tile grid
 // (blockIdx for the hardware-dispatched kernels).
 template <int SC, bool COUNT, int K, typename OUT>

@@ -101,6 +101,13 @@ int pick_kernel(const rm_params &p) {
     return rm::KERNEL_TILE8;  // 0 auto, 2: measured fastest on every config
 }
 
+// the pose's four plane rotations keep a direction's length (rm_far_sky.h unit_rotation): glsl_cos and glsl_sin
+// of one angle do, until the angle is so large that x + pi/2 no longer resolves
+static bool pose_keeps_unit(const FrameConst &F) {
+    return rmfs::unit_rotation(F.cam1_c, F.cam1_s) && rmfs::unit_rotation(F.cam2_c, F.cam2_s) &&
+           rmfs::unit_rotation(F.ry_c, F.ry_s) && rmfs::unit_rotation(F.rx_c, F.rx_s);
+}
+
 // The members of F that depend on the pose (u_pos, u_mouse, u_time) and nothing
 // else: frame_const below calls it with the context's pose, a view batch
 // (rm_batch_host.cpp) once per view with the view's -- one body under this
@@ -118,6 +125,9 @@ void pose_const(FrameConst &F, const float pos[3], const float mouse[2], float t
     F.ry_c = rm::glsl_cos(ay); F.ry_s = rm::glsl_sin(ay);
     F.rx_c = rm::glsl_cos(ax); F.rx_s = rm::glsl_sin(ax);
     rm::camera_sponge_origin(F);  // (after pos and the sponge rotation)
+    // the near-sky ladder is proved for directions of unit length (rm_far_sky.h 3.): a pose whose rotations do not
+    // keep it takes the launch's radius back to the far-sky cube's (near_sky_radius; a view batch: any view's)
+    if (F.near_r > 0.0f && !pose_keeps_unit(F)) F.near_r = rmfs::near_sky_radius(F.max_steps, false);
     F.time = time;
     F.mouse_x = mouse[0];
     F.mouse_y = mouse[1];
@@ -131,14 +141,17 @@ FrameConst frame_const(const rm_ctx *c, int W, int H, const RowPart &part, int n
     std::memset(&F, 0, sizeof(F));
     F.res_x = c->res_set ? c->res[0] : (float)W;
     F.res_y = c->res_set ? c->res[1] : (float)H;
+    // (before pose_const, which withdraws the ladder's radius under a pose it is not proved for)
+    F.max_steps = c->params.max_steps;
+    F.near_r = c->scene == rm::SCENE_T ? rmfs::near_sky_radius(F.max_steps, true) : 0.0f;
     pose_const(F, c->pos, c->mouse, c->time);
     F.W = W; F.H = H;
     F.cycle = part.cycle; F.offset = part.offset; F.run = part.run; F.nrows = nrows;
     F.run_magic = rm::div_magic((uint32_t)part.run, (uint64_t)H + 1);  // packed rows j < H
-    F.max_steps = c->params.max_steps;
     // 0 (unbounded, the reference) travels as INT_MAX: one compare per shadow step
     F.shadow_max_steps = c->params.shadow_max_steps > 0 ? c->params.shadow_max_steps : 0x7fffffff;
-    // the far-sky shortcut's proof needs max_steps >= N0 (rm_far_sky.h); any other step cap marches every ray
+    // the far-sky vote of the instrumented kernels, behind rm_stats.skipped: max_steps >= N0 (rm_far_sky.h).  The
+    // timed kernels vote at F.near_r (above)
     F.far_sky = c->scene == rm::SCENE_T && F.max_steps >= rmfs::kFarSkyN0 ? 1 : 0;
     F.lat_tiles = lat_tiles_for(pick_kernel(c->params), W, nrows);
     for (int i = 0; i < 32; i++) {
@@ -224,8 +237,9 @@ rm_status render_dev(rm_ctx *ctx, int W, int H, const RowPart &part, int row0, i
     }
     ctx->last_certified = 0;  // rm_certified_steps(): of this launch alone, set below when it is counted
     ctx->last_refl_cleared = 0;  // rm_reflection_cleared_steps(): likewise
+    ctx->last_near_sky = 0;      // rm_near_sky_steps(): likewise
     bool cnt = ctx->params.count_evals != 0 || evmap;
-    if (cnt) RM_HIP(hipMemsetAsync(ctx->d_evals, 0, 5 * sizeof(unsigned long long), ctx->stream));
+    if (cnt) RM_HIP(hipMemsetAsync(ctx->d_evals, 0, 6 * sizeof(unsigned long long), ctx->stream));
     if (stats) RM_HIP(hipEventRecord(ctx->ev0, ctx->stream));
     hipError_t e =
         wire ? rm::launch_render_wire(ctx->scene, F, static_cast<rm::WireTile *>(out), cnt ? ctx->d_evals : nullptr,
@@ -257,7 +271,7 @@ rm_status render_dev(rm_ctx *ctx, int W, int H, const RowPart &part, int row0, i
         RM_HIP(hipEventSynchronize(ctx->ev1));
         float ms = 0.0f;
         RM_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-        unsigned long long ev[5] = {0, 0, 0, 0, 0};
+        unsigned long long ev[6] = {0, 0, 0, 0, 0, 0};
         if (cnt) RM_HIP(hipMemcpy(ev, ctx->d_evals, sizeof(ev), hipMemcpyDeviceToHost));
         std::memset(stats, 0, sizeof(*stats));
         stats->evals = ev[0];
@@ -265,6 +279,7 @@ rm_status render_dev(rm_ctx *ctx, int W, int H, const RowPart &part, int row0, i
         stats->skipped = ev[2];
         ctx->last_certified = ev[3];  // (0 when not counted)
         ctx->last_refl_cleared = ev[4];
+        ctx->last_near_sky = ev[5];
         stats->pixels = (uint64_t)W * (uint64_t)count;
         stats->kernel_ms = ms;
         stats->scene = ctx->scene;

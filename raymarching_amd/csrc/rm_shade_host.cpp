@@ -35,6 +35,7 @@ rm_status shade_dev(rm_ctx *ctx, const FrameConst &F, const rm::ShadeRays &Q, rm
         stats->pixels = (uint64_t)Q.n;
         ctx->last_certified = 0;  // (rm_certified_steps: the shade kernels are not instrumented)
         ctx->last_refl_cleared = 0;
+        ctx->last_near_sky = 0;
         stats->kernel_ms = ms;
         stats->scene = ctx->scene;
     }
