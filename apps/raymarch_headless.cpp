@@ -25,7 +25,11 @@
 // line, px py pz mx my t [ox oy] (u_pos, u_mouse, u_time and an optional
 // sub-pixel offset), all rendered at --w x --h by one launch on one GPU.  With
 // --ppm NAME it writes NAME.0000.ppm, NAME.0001.ppm, ...; with --stats the JSON
-// line carries the launch's kernel_ms.
+// line carries the launch's kernel_ms.  With --aa K[:threshold] the batch is
+// rendered antialiased (rm::Shader::renderBatchAA -> rm_render_batch_aa_rgba8,
+// every view's offset (0, 0)): the JSON line gains "aa": K and "refined": the
+// pixels refined over all views, and kernel_ms sums the batch, detect + plan
+// and refine launches.
 // --fisheye fov_deg writes --ppm from the fisheye camera main() carries
 // commented out (output_shader.frag:396-400) instead of the pinhole's frame:
 // after the last frame its w x h rays are built here on the host, from the
@@ -298,15 +302,21 @@ int main(int argc, char** argv) {
         std::vector<uint32_t> px((size_t)n * w * h);  // a host target: staged, written when the call returns
         rm_stats st;
         std::memset(&st, 0, sizeof(st));
+        rm_aa_stats aa_st;  // --aa: always taken, for the JSON line's "refined"
+        std::memset(&aa_st, 0, sizeof(aa_st));
         const auto b0 = std::chrono::steady_clock::now();
-        if (!shader.renderBatch(w, h, views.data(), n, px.data(), stats ? &st : nullptr)) {
+        if (aa_samples ? !shader.renderBatchAA(w, h, views.data(), n, px.data(), aa_samples, aa_threshold, nullptr,
+                                               nullptr, &aa_st)
+                       : !shader.renderBatch(w, h, views.data(), n, px.data(), stats ? &st : nullptr)) {
             std::fprintf(stderr, "--views failed: %s\n", shader.lastError().c_str());
             return 1;
         }
+        if (aa_samples) st.kernel_ms = aa_st.base_ms + aa_st.detect_ms + aa_st.refine_ms;
         const double wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - b0).count();
         std::printf("{\"views\": %d, \"w\": %d, \"h\": %d, \"scene\": \"%s\", \"format\": \"rgba8\", \"wall_ms\": %.3f", n, w,
                     h, scene.c_str(), wall_ms);
         if (stats) std::printf(", \"kernel_ms\": %.4f", st.kernel_ms);
+        if (aa_samples) std::printf(", \"aa\": %d, \"refined\": %lld", aa_samples, (long long)aa_st.refined);
         std::printf("}\n");
         for (int v = 0; v < n && !ppm.empty(); v++) {
             char suffix[32];

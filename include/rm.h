@@ -529,7 +529,8 @@ rm_status rm_render_aa_rgba8(rm_ctx *ctx, int W, int H, const rm_aa_params *para
  *   Out of scope: scene plugins and per-view plugin uniforms; count_evals and
  * step maps per view; an adaptive or costliest-first order across views; views
  * of different sizes in one batch; device-resident view arrays; multi-GPU
- * batches; adaptive supersampling of batched frames. */
+ * batches.  (Adaptive supersampling of batched frames: rm_render_batch_aa_rgba8
+ * below.) */
 typedef struct rm_view {
     float pos[3];    /* u_pos   */
     float mouse[2];  /* u_mouse */
@@ -541,6 +542,55 @@ rm_status rm_batch_bytes(int W, int H, int n, int rgba8, int64_t *frame_bytes, i
 rm_status rm_render_batch(rm_ctx *ctx, int W, int H, const rm_view *views, int n, float *out, rm_stats *stats);
 rm_status rm_render_batch_rgba8(rm_ctx *ctx, int W, int H, const rm_view *views, int n, uint32_t *out,
                                 rm_stats *stats);
+
+/* Adaptive supersampling of a view batch: n antialiased RGBA8 frames from one
+ * call -- the batch launch, then detect, plan and refine launches over all the
+ * views, with no host round trip.  View v's frame is at
+ * out + v * W * H words, and every byte of it is what rm_render_aa_rgba8 writes
+ * after u_pos, u_mouse and u_time are set to the view's values, with the same
+ * rm_aa_params (edge rule, samples and sum: see rm_render_aa_rgba8 above).
+ *   mask: NULL or n * W * H bytes; view v's part is the single call's mask.
+ * refined: NULL or n words; word v is the single call's rm_aa_stats.refined for
+ * view v.
+ * rm_refine_batch_rgba8: the same relation to rm_refine_rgba8 -- it replaces the
+ * edge pixels of the n given frames in place and reads nothing else from them.
+ * rm_render_batch_aa_rgba8: rm_render_batch_rgba8 into `out`, then
+ * rm_refine_batch_rgba8 of it.
+ *   As for a view batch: `views` is a host pointer read during the call;
+ * u_resolution, rm_params.max_steps and shadow_max_steps are the context's; the
+ * context's own u_pos, u_mouse, u_time and u_seed1 are neither read nor changed.
+ * frames / out, mask and refined are all device pointers (asynchronous on the
+ * ctx stream unless `stats` is given) or all host pointers (staged; the call
+ * returns when the results are written).  With `stats` the call waits and fills
+ * it: refined the sum over the views, base_ms the batch launch, detect_ms the
+ * detect and plan launches, refine_ms the refine launch.
+ *   Size rule, checked by all three calls before any pointer is used: the view
+ * batch's rule (W, H > 0; 0 <= n <= 65535; ceil(H / 8) <= 65535; n * W * H <= 2^31)
+ * and W * H < 2^30.
+ *   Errors, in this order: the size rule broken, a NULL params, a NULL views or
+ * frames with n > 0, samples not 2, 4 or 8, a threshold outside 0..255, or a
+ * view whose offset is not exactly (0, 0) (the samples' offsets take the place
+ * of the fragment offset, and a sum of the two is not exact in f32):
+ * RM_ERR_INVALID_ARGUMENT; no scene: RM_ERR_NO_SCENE; a scene plugin:
+ * RM_ERR_SCENE ("batch supersampling: built-in scenes only"), the target
+ * untouched; n = 0: RM_OK, nothing launched, stats zeroed; mixed host and
+ * device pointers: RM_ERR_INVALID_ARGUMENT.
+ *   The counters, the plan and the queue are one scratch buffer of the context
+ * with the life and stream rule of rm_bloom's.  rm_batch_aa_scratch_bytes (host
+ * only, no GPU) returns its size under the same size rule:
+ *     4 * (32 * n + roundup32(n + 2) + n * W * H) bytes
+ * -- a 128-byte line per view for its counter, the plan's n + 2 words (the
+ * exclusive prefix of the views' group counts, the groups' total, the counts'
+ * total) rounded up to a line, and a queue word per pixel; `bytes` may be NULL.
+ * The view records are the view batch's own scratch.
+ *   Out of scope: scene plugins, float targets, a threshold or sample count per
+ * view, views of different sizes, multi-GPU batches and count_evals of the
+ * refine. */
+rm_status rm_batch_aa_scratch_bytes(int W, int H, int n, int64_t *bytes);
+rm_status rm_refine_batch_rgba8(rm_ctx *ctx, int W, int H, const rm_view *views, int n, const rm_aa_params *params,
+                                uint32_t *frames, uint8_t *mask, uint32_t *refined, rm_aa_stats *stats);
+rm_status rm_render_batch_aa_rgba8(rm_ctx *ctx, int W, int H, const rm_view *views, int n, const rm_aa_params *params,
+                                   uint32_t *out, uint8_t *mask, uint32_t *refined, rm_aa_stats *stats);
 
 /* rm_render_band / rm_render_rows into RGBA8 rows (W uint32 per row). */
 rm_status rm_render_band_rgba8(rm_ctx *ctx, int W, int H, int band, int nshards, int shard, uint32_t *out,

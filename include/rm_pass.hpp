@@ -142,6 +142,18 @@ public:
     bool renderBatch(int w, int h, const rm_view* views, int n, float* out, rm_stats* stats = nullptr) {
         return ctx_ && rm_render_batch(ctx_, w, h, views, n, out, stats) == RM_OK;
     }
+    // rm.h rm_render_batch_aa_rgba8: renderBatch's RGBA8 frames with every view's
+    // edge pixels supersampled, view v's frame what setUniform(pose) +
+    // RenderTexture::drawAA(shader, samples, threshold) gives.  mask (n * w * h
+    // bytes) and refined (n words, the views' counts of refined pixels) may be
+    // null; they live where `out` does (all device or all host pointers).  Every
+    // view's offset must be (0, 0).
+    bool renderBatchAA(int w, int h, const rm_view* views, int n, std::uint32_t* out, int samples = 4,
+                       int threshold = 32, std::uint8_t* mask = nullptr, std::uint32_t* refined = nullptr,
+                       rm_aa_stats* stats = nullptr) {
+        const rm_aa_params p{samples, threshold};
+        return ctx_ && rm_render_batch_aa_rgba8(ctx_, w, h, views, n, &p, out, mask, refined, stats) == RM_OK;
+    }
 
 private:
     bool setArray(const char* name, int components, const float* v, std::size_t length) {

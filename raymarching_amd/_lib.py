@@ -36,7 +36,8 @@ EXPORTS = ("rm_create", "rm_destroy", "rm_load_scene", "rm_set_uniform1f", "rm_s
            "rm_aa_offsets", "rm_aa_edge_mask", "rm_refine_rgba8", "rm_render_aa_rgba8", "rm_shade_rays", "rm_scene_eval_form",
            "rm_resolution_cache_info", "rm_certified_steps", "rm_reflection_cleared_steps",
            "rm_near_sky_steps",
-           "rm_batch_bytes", "rm_render_batch", "rm_render_batch_rgba8")
+           "rm_batch_bytes", "rm_render_batch", "rm_render_batch_rgba8",
+           "rm_batch_aa_scratch_bytes", "rm_refine_batch_rgba8", "rm_render_batch_aa_rgba8")
 
 # include/rm.h RM_ABI_VERSION: the struct layouts below
 ABI_VERSION = 3
@@ -203,6 +204,11 @@ def lib() -> ctypes.CDLL:
         "rm_batch_bytes": ([c.c_int, c.c_int, c.c_int, c.c_int, c.POINTER(c.c_int64), c.POINTER(c.c_int64)], c.c_int),
         "rm_render_batch": ([vp, c.c_int, c.c_int, vp, c.c_int, vp, c.POINTER(RmStats)], c.c_int),
         "rm_render_batch_rgba8": ([vp, c.c_int, c.c_int, vp, c.c_int, vp, c.POINTER(RmStats)], c.c_int),
+        "rm_batch_aa_scratch_bytes": ([c.c_int, c.c_int, c.c_int, c.POINTER(c.c_int64)], c.c_int),
+        "rm_refine_batch_rgba8": ([vp, c.c_int, c.c_int, vp, c.c_int, c.POINTER(RmAaParams), vp, vp, vp,
+                                   c.POINTER(RmAaStats)], c.c_int),
+        "rm_render_batch_aa_rgba8": ([vp, c.c_int, c.c_int, vp, c.c_int, c.POINTER(RmAaParams), vp, vp, vp,
+                                      c.POINTER(RmAaStats)], c.c_int),
         "rm_shade_rays": ([vp, vp, c.c_int, vp, c.c_int64, c.POINTER(RmShadeParams), vp, vp, c.POINTER(RmStats)],
                           c.c_int),
         "rm_sharded_layout": ([c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.POINTER(RmShardLayout)], c.c_int),

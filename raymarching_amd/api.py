@@ -733,6 +733,69 @@ class Renderer:
         H, W = frame8.shape
         return self._aa(lib().rm_refine_rgba8, W, H, samples, threshold, frame8, mask, stats)
 
+    # --- adaptive supersampling of a view batch (rm_render_batch_aa_rgba8, rm_refine_batch_rgba8) ---
+    def _batch_aa(self, fn, W, H, views, samples, threshold, frames8, mask, refined, stats):
+        """frames8: [n, H, W] RGBA8 words, a device tensor or a numpy array
+        (staged); the mask and the per-view counts live where the frames do.
+        -> frames8[, mask][, refined][, stats]."""
+        import numpy as np
+        v = pack_views(views)
+        n = len(v)
+        on_device = hasattr(frames8, "data_ptr")
+        _check_out(frames8, n * H * W)
+        m = r = None
+        if mask:
+            m = (_torch().empty((n, H, W), dtype=_torch().uint8, device=frames8.device) if on_device
+                 else np.empty((n, H, W), np.uint8))
+        if refined:
+            r = (_torch().empty((n,), dtype=_torch().int32, device=frames8.device) if on_device
+                 else np.empty((n,), np.uint32))
+        p = _lib.RmAaParams(int(samples), int(threshold))
+        s = _lib.RmAaStats()
+        check(fn(self._ctx, int(W), int(H), ctypes.c_void_p(v.ctypes.data), n, ctypes.byref(p), self._ptr(frames8),
+                 self._ptr(m) if mask else None, self._ptr(r) if refined else None,
+                 ctypes.byref(s) if stats else None), self._ctx)
+        res = (frames8,) + ((m,) if mask else ()) + ((r,) if refined else ()) + ((s.as_dict(),) if stats else ())
+        return res if len(res) > 1 else frames8
+
+    def render_batch_aa(self, W: int, H: int, views, samples=4, threshold=32, out=None, mask=False, refined=False,
+                        stats=False):
+        """n antialiased RGBA8 views from one call (rm_render_batch_aa_rgba8;
+        DESIGN.md 2.28): render_batch's frames with every view's edge pixels
+        supersampled, view v's frame byte for byte what set_pose + render_aa
+        gives with the same samples and threshold.  views: as render_batch
+        takes them, every offset (0, 0).  out: [n, H, W] int32 device tensor
+        (allocated if None; asynchronous on the renderer's stream unless
+        stats=True) or a numpy array (staged).  Returns out, then with
+        mask=True the uint8 [n, H, W] mask of the refined pixels, then with
+        refined=True the [n] per-view counts of refined pixels (int32 on the
+        device, uint32 in numpy), then with stats=True dict(refined, base_ms,
+        detect_ms, refine_ms) -- refined summed over the views, detect_ms with
+        the plan step (which waits for the frames).  Built-in scenes only."""
+        if out is None:
+            out = _torch().empty((len(pack_views(views)), H, W), dtype=_torch().int32, device=f"cuda:{self.device}")
+        return self._batch_aa(lib().rm_render_batch_aa_rgba8, W, H, views, samples, threshold, out, mask, refined,
+                              stats)
+
+    def refine_batch(self, frames8, views, samples=4, threshold=32, mask=False, refined=False, stats=False):
+        """rm_refine_batch_rgba8: the supersampling step of render_batch_aa on
+        any [n, H, W] RGBA8 frames of the views (normally render_batch's), in
+        place; returns as render_batch_aa does."""
+        n, H, W = frames8.shape
+        if n != len(pack_views(views)):
+            raise ValueError(f"refine_batch: {n} frames for {len(pack_views(views))} views")
+        return self._batch_aa(lib().rm_refine_batch_rgba8, W, H, views, samples, threshold, frames8, mask, refined,
+                              stats)
+
+
+def batch_aa_scratch_bytes(W: int, H: int, n: int) -> int:
+    """rm_batch_aa_scratch_bytes: the bytes of the renderer's scratch buffer
+    (counters, plan, queue) for render_batch_aa of n views of W x H; RmError
+    where the size rule refuses them.  No GPU."""
+    b = ctypes.c_int64(0)
+    check(lib().rm_batch_aa_scratch_bytes(int(W), int(H), int(n), ctypes.byref(b)))
+    return int(b.value)
+
 
 def pack_views(views):
     """The views of Renderer.render_batch as the contiguous float32 [n, 8]

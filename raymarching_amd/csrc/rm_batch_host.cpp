@@ -54,11 +54,17 @@ rm_status batch_scratch(rm_ctx *ctx, size_t bytes) {
     return RM_OK;
 }
 
-// the upload and the one launch, on the context's stream; `out` a device pointer
-rm_status batch_dev(rm_ctx *ctx, int W, int H, const rm_view *views, int n, void *out, bool rgba8, rm_stats *stats) {
+}  // namespace
+
+namespace rmhost {
+
+// The launch's shared constants and the upload of the per-view records, on the
+// context's stream (rm_ctx.h): what a view batch and its supersampling
+// (rm_batch_aa_host.cpp) both start with.
+rm_status batch_records(rm_ctx *ctx, int W, int H, const rm_view *views, int n, FrameConst &F, const void *&rec_d) {
     RowPart part;
     (void)rm::band_part(H, 1, 0, part);  // the whole frame, as rm_render's launch
-    FrameConst F = frame_const(ctx, W, H, part, H);
+    F = frame_const(ctx, W, H, part, H);
     if (rm_status st = frame_rcp(ctx, F)) return st;  // (one lookup per call: the resolution is shared)
     F.row0 = 0;
     F.tile_run = rm::wave_row_mode(part, 0, 8, F.run_magic != 0);
@@ -78,14 +84,19 @@ rm_status batch_dev(rm_ctx *ctx, int W, int H, const rm_view *views, int n, void
     }
     F.near_r = V.near_r;  // (shared by the views: pose_const withdraws the ladder's radius if any view's pose asks it)
     if (rm_status st = batch_scratch(ctx, bytes)) return st;
-    void *rec_d = ctx->batch_views;
-    RM_HIP(hipMemcpyAsync(rec_d, slot->host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    rec_d = ctx->batch_views;
+    RM_HIP(hipMemcpyAsync(ctx->batch_views, slot->host, bytes, hipMemcpyHostToDevice, ctx->stream));
     RM_HIP(hipEventRecord(slot->copied, ctx->stream));
     slot->used = true;
     ctx->batch_stream = ctx->stream;
     ctx->batch_pending = true;
     mark_done(ctx);
+    return RM_OK;
+}
 
+// the one launch over views x tiles; F, rec_d: batch_records'; `out` a device pointer
+rm_status batch_launch(rm_ctx *ctx, const FrameConst &F, const void *rec_d, int n, void *out, bool rgba8,
+                       rm_stats *stats) {
     ctx->last_certified = 0;  // (of the last render launch alone; this one counts nothing)
     ctx->last_refl_cleared = 0;
     ctx->last_near_sky = 0;
@@ -100,12 +111,24 @@ rm_status batch_dev(rm_ctx *ctx, int W, int H, const rm_view *views, int n, void
         float ms = 0.0f;
         RM_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
         std::memset(stats, 0, sizeof(*stats));
-        stats->pixels = (uint64_t)n * (uint64_t)W * (uint64_t)H;
+        stats->pixels = (uint64_t)n * (uint64_t)F.W * (uint64_t)F.H;
         stats->kernel_ms = ms;
         stats->scene = ctx->scene;
         stats->dispatch = RM_DISPATCH_ROW_MAJOR;
     }
     return RM_OK;
+}
+
+}  // namespace rmhost
+
+namespace {
+
+// the upload and the one launch, on the context's stream; `out` a device pointer
+rm_status batch_dev(rm_ctx *ctx, int W, int H, const rm_view *views, int n, void *out, bool rgba8, rm_stats *stats) {
+    FrameConst F;
+    const void *rec_d = nullptr;
+    if (rm_status st = batch_records(ctx, W, H, views, n, F, rec_d)) return st;
+    return batch_launch(ctx, F, rec_d, n, out, rgba8, stats);
 }
 
 rm_status batch_run(rm_ctx *ctx, int W, int H, const rm_view *views, int n, void *out, bool rgba8, rm_stats *stats) {

@@ -104,6 +104,8 @@ rm_status rm_destroy(rm_ctx *ctx) {
     if (ctx->aa_queue) (void)hipFree(ctx->aa_queue);
     if (ctx->aa_ev) (void)hipEventDestroy(ctx->aa_ev);
     if (ctx->aa_ev2) (void)hipEventDestroy(ctx->aa_ev2);
+    if (ctx->baa_scratch) (void)hipFree(ctx->baa_scratch);
+    if (ctx->baa_ev) (void)hipEventDestroy(ctx->baa_ev);
     if (ctx->batch_views) (void)hipFree(ctx->batch_views);
     if (ctx->batch_ev) (void)hipEventDestroy(ctx->batch_ev);
     for (auto &b : ctx->batch_slot) {  // (wait_idle above: no upload still reads a block)

@@ -107,6 +107,13 @@ struct rm_ctx {
     static constexpr int kBatchSlots = 4;
     BatchSlot batch_slot[kBatchSlots];
     int batch_next = 0;
+    // adaptive supersampling of a view batch (rm_batch_aa_host.cpp): the counters, the plan and the queue
+    // (rm_batch_aa_plan.h layout), one buffer per context, grown on demand, with bloom's stream rule as above
+    uint32_t *baa_scratch = nullptr;
+    size_t baa_words = 0;
+    hipEvent_t baa_ev = nullptr;
+    hipStream_t baa_stream = nullptr;
+    bool baa_pending = false;
     // FrameConst.rcp_* of scenes S0/T (rm_render_host.cpp frame_rcp): the device's reciprocals of the frame
     // size and of u_resolution.y, kept per resolution -- the key changes when a window is resized, not per frame
     // (u_time and the pose do not enter it).  A small fixed-size cache, least recently used out, so that callers
@@ -238,5 +245,14 @@ rm_status render_part(rm_ctx *ctx, int W, int H, const rm::RowPart &part, int ro
                       bool rgba8, rm_stats *stats, uint32_t *evmap = nullptr, bool accum = false);
 rm_status render_any(rm_ctx *ctx, int W, int H, int band, int nshards, int shard, int row_begin, int row_count,
                      void *out, bool rgba8, rm_stats *stats, uint32_t *evmap = nullptr, bool accum = false);
+
+
+// ---- rm_batch_host.cpp
+// a view batch's shared constants F (W x H, row-major) and the upload of its n per-view records (rm_batch.h) on
+// the context's stream, then its one launch into the device pointer `out`: rm_render_batch's two halves, which
+// rm_batch_aa_host.cpp calls too (a refine alone takes the records without the launch)
+rm_status batch_records(rm_ctx *ctx, int W, int H, const rm_view *views, int n, rm::FrameConst &F, const void *&rec_d);
+rm_status batch_launch(rm_ctx *ctx, const rm::FrameConst &F, const void *rec_d, int n, void *out, bool rgba8,
+                       rm_stats *stats);
 
 }  // namespace rmhost

@@ -204,6 +204,13 @@ rm_status set_stream(rm_ctx *ctx, hipStream_t s) {
         RM_HIP(hipEventRecord(ctx->batch_ev, ctx->stream));
         ctx->batch_pending = false;
     }
+    if (s != ctx->stream && ctx->baa_pending && ctx->baa_stream == ctx->stream) {
+        // the same for the last batch supersampling's scratch (rm_batch_aa_host.cpp batch_aa_scratch)
+        RM_HIP(hipSetDevice(ctx->device));
+        if (!ctx->baa_ev) RM_HIP(hipEventCreateWithFlags(&ctx->baa_ev, hipEventDisableTiming));
+        RM_HIP(hipEventRecord(ctx->baa_ev, ctx->stream));
+        ctx->baa_pending = false;
+    }
 #ifdef RM_ANALYSIS_LEAVE_NO_RECORD
     // analysis builds only (-DRM_ANALYSIS_LEAVE_NO_RECORD, tools/scale_model.py
     // prices the marker with it; unsafe: a later release of a schedule buffer or
