@@ -16,7 +16,8 @@
 // from L1/L2; 4 B in + 4 B out of HBM per pixel).
 //
 // Blocks whose span is short output their centre texel without the span taps
-// (proof at the test): 0.069-0.072 -> 0.052-0.053 ms on the C3 frame, same
+// (proof at the test, tests/test_fxaa_claims.py::
+// test_short_span_outputs_centre_texel): 0.069-0.072 -> 0.052-0.053 ms on the C3 frame, same
 // bits (profiles/r05/fxaa_flat/); with 8x8-pixel blocks per wave pass instead
 // of rows, 0.046-0.047 (profiles/r05/fxaa_blocks/); a halo of 4 (its rows are
 // then 72 words, 8 banks apart: a block's 8 x 8 reads hit 64 distinct banks)
