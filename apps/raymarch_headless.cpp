@@ -29,7 +29,11 @@
 // rendered antialiased (rm::Shader::renderBatchAA -> rm_render_batch_aa_rgba8,
 // every view's offset (0, 0)): the JSON line gains "aa": K and "refined": the
 // pixels refined over all views, and kernel_ms sums the batch, detect + plan
-// and refine launches.
+// and refine launches.  With --post [--post-sample ..] [--tonemap ..] the batch
+// (antialiased or not) is rendered into a device target and the post passes run
+// over all its views at once (rm::PostShader::drawChainBatch ->
+// rm_post_chain_batch): --ppm then writes the post-processed frames and the
+// JSON line gains "post": true.
 // --fisheye fov_deg writes --ppm from the fisheye camera main() carries
 // commented out (output_shader.frag:396-400) instead of the pinhole's frame:
 // after the last frame its w x h rays are built here on the host, from the
@@ -304,12 +308,35 @@ int main(int argc, char** argv) {
         std::memset(&st, 0, sizeof(st));
         rm_aa_stats aa_st;  // --aa: always taken, for the JSON line's "refined"
         std::memset(&aa_st, 0, sizeof(aa_st));
+        // --post: the batch is rendered into a device target, and main.cpp:209-214's post passes run over all
+        // its views at once (rm_post_chain_batch); the frames written are the post-processed ones
+        uint32_t* dev = nullptr;  // frames | post.frag's output | bloom's output
+        if (post && n > 0 && hipMalloc(&dev, 3 * px.size() * sizeof(uint32_t)) != hipSuccess) {
+            std::fprintf(stderr, "cannot allocate the device targets of %d %dx%d views\n", n, w, h);
+            return 1;
+        }
+        uint32_t* target = dev ? dev : px.data();
         const auto b0 = std::chrono::steady_clock::now();
-        if (aa_samples ? !shader.renderBatchAA(w, h, views.data(), n, px.data(), aa_samples, aa_threshold, nullptr,
+        if (aa_samples ? !shader.renderBatchAA(w, h, views.data(), n, target, aa_samples, aa_threshold, nullptr,
                                                nullptr, &aa_st)
-                       : !shader.renderBatch(w, h, views.data(), n, px.data(), stats ? &st : nullptr)) {
+                       : !shader.renderBatch(w, h, views.data(), n, target, stats ? &st : nullptr)) {
             std::fprintf(stderr, "--views failed: %s\n", shader.lastError().c_str());
             return 1;
+        }
+        if (dev) {
+            rm::PostShader post_shader(shader);
+            if (!rm::ShaderLoader::loadFromFile("post.frag", rm::Shader::Fragment, post_shader)) return 1;
+            post_shader.setUniform("u_resolution", rm::Vec2{wf, hf});
+            post_shader.setSample(post_sample);
+            post_shader.setTonemap(tonemap);
+            if (!post_shader.drawChainBatch(dev, dev + px.size(), dev + 2 * px.size(), n) ||
+                rm_synchronize(shader.ctx()) != RM_OK ||
+                hipMemcpy(px.data(), dev + 2 * px.size(), px.size() * sizeof(uint32_t), hipMemcpyDeviceToHost) !=
+                    hipSuccess) {
+                std::fprintf(stderr, "--views --post failed: %s\n", post_shader.lastError().c_str());
+                return 1;
+            }
+            (void)hipFree(dev);
         }
         if (aa_samples) st.kernel_ms = aa_st.base_ms + aa_st.detect_ms + aa_st.refine_ms;
         const double wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - b0).count();
@@ -317,6 +344,7 @@ int main(int argc, char** argv) {
                     h, scene.c_str(), wall_ms);
         if (stats) std::printf(", \"kernel_ms\": %.4f", st.kernel_ms);
         if (aa_samples) std::printf(", \"aa\": %d, \"refined\": %lld", aa_samples, (long long)aa_st.refined);
+        if (post) std::printf(", \"post\": true");
         std::printf("}\n");
         for (int v = 0; v < n && !ppm.empty(); v++) {
             char suffix[32];

@@ -659,6 +659,74 @@ rm_status rm_post_frag(rm_ctx *ctx, int W, int H, int sample, int tonemap, const
 rm_status rm_post_chain_ex(rm_ctx *ctx, int W, int H, int sample, int tonemap, const uint32_t *in, uint32_t *mid,
                            uint32_t *out);
 
+/* The post passes over a batch: n equally sized RGBA8 frames packed as a view
+ * batch packs them (view v's frame at p + v * W * H words), every view
+ * processed by the same few launches -- their number does not grow with n,
+ * apart from the groups below.  Every byte of view v is what
+ * the single-frame call writes for that frame:
+ *   rm_post_frag_batch   view v = rm_post_frag(in_v -> out_v) with the same
+ *                        sample and tonemap; (FXAA, NONE) = rm_fxaa
+ *   rm_bloom_batch       view v = rm_bloom(in_v -> out_v)
+ *   rm_post_chain_batch  rm_post_frag_batch(in -> mid), then
+ *                        rm_bloom_batch(mid -> out): view v = rm_post_chain_ex,
+ *                        and with (FXAA, NONE) rm_post_chain
+ * u_resolution = (W, H) for every view, and every view is flipped vertically
+ * by itself, as the single call flips its frame.  All buffers are device
+ * pointers; the calls are asynchronous on the context's stream.  No scene
+ * needs to be loaded.
+ *   Size rule, checked before any pointer is used: W, H > 0; 0 <= n <= 65535;
+ * n * W * H <= 2^31; W * H < 2^30.  Then: a sample or tonemap value outside its
+ * enum; n = 0: RM_OK, nothing launched; a NULL buffer; buffers whose ranges
+ * [p, p + n * W * H) are not pairwise disjoint; a host pointer -- each
+ * RM_ERR_INVALID_ARGUMENT with nothing written.
+ *   Scratch: bloom's per-frame scratch is large for small frames (at 64 x 64
+ * about 390 KB per view against a 16 KB frame), so the views go through the
+ * context's bloom buffer (rm_bloom's, with its life and stream rule) in groups.
+ * With P = bloom's single-frame layout for W x H,
+ *     shared_bytes   = the bytes of P: what rm_bloom itself keeps for W x H.
+ *                      A batch uses its run tables, which depend on W x H only,
+ *                      are built once for all views and are kept for the next
+ *                      batch or single bloom of this size on this stream;
+ *     per_view_bytes = 4 * (roundup4(texels of mip levels 1..d2)
+ *                           + 12 * (runs_x(d1) * runs_y(d1) + runs_x(d2) * runs_y(d2)))
+ *                      -- the view's mip levels and the run-pair polynomials of
+ *                      the two levels bloom.frag reads, runs(axis) = min(pixels
+ *                      along it, 5 * the level's size along it + 1); 0 for
+ *                      H <= 20, where bloom reads the frame alone;
+ *     group_views    = max(1, min(n, (limit - shared_bytes) / per_view_bytes))
+ *                      (n where per_view_bytes is 0);
+ *     groups         = ceil(n / group_views);
+ *     scratch_bytes  = shared_bytes + group_views * per_view_bytes: what the
+ *                      call makes sure the buffer holds (0 for n = 0);
+ *     launches       = groups * (1 + the launches of one bloom: a mip launch per
+ *                      level or one pyramid launch, then two) + 1 for the run
+ *                      tables: the kernel launches of one rm_post_chain_batch on
+ *                      a context that has not bloomed this size (0 for n = 0).
+ * rm_post_batch_plan (host only, no GPU) returns these under the size rule;
+ * limit_bytes 0 means the default, RM_POST_BATCH_SCRATCH_DEFAULT; negative:
+ * RM_ERR_INVALID_ARGUMENT; `out` may be NULL.
+ * rm_set_post_batch_scratch_limit sets the context's limit (0 restores the
+ * default); a view that alone exceeds it is still processed, in a group of 1.
+ *   Out of scope: host pointers, views of different sizes, a sample or tonemap
+ * per view, multi-GPU batches, float targets, a fused render + post launch. */
+#define RM_POST_BATCH_SCRATCH_DEFAULT ((int64_t)512 << 20) /* 512 MiB */
+struct rm_post_batch_plan {
+    int64_t per_view_bytes;
+    int64_t shared_bytes;
+    int32_t group_views;
+    int32_t groups;
+    int64_t scratch_bytes;
+    int32_t launches;
+    int32_t reserved; /* 0 */
+};
+rm_status rm_post_batch_plan(int W, int H, int n, int64_t limit_bytes, struct rm_post_batch_plan *out);
+rm_status rm_set_post_batch_scratch_limit(rm_ctx *ctx, int64_t bytes);
+rm_status rm_post_frag_batch(rm_ctx *ctx, int W, int H, int n, int sample, int tonemap, const uint32_t *in,
+                             uint32_t *out);
+rm_status rm_bloom_batch(rm_ctx *ctx, int W, int H, int n, const uint32_t *in, uint32_t *out);
+rm_status rm_post_chain_batch(rm_ctx *ctx, int W, int H, int n, int sample, int tonemap, const uint32_t *in,
+                              uint32_t *mid, uint32_t *out);
+
 /* Scenes S0/T keep the device's reciprocals of the frame size and of
  * u_resolution.y per resolution (W, H, u_resolution.y) in a small cache of the
  * context: the first render of a new resolution runs a one-thread kernel on the

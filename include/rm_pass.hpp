@@ -199,6 +199,22 @@ public:
         error_ = msg;
         return false;
     }
+    // The pass over n frames of u_resolution packed one after the other in
+    // device memory, such as a view batch's (rm_post_frag_batch): view v of
+    // `dst` is RenderTexture::draw(post) of view v of `src`.  drawChainBatch:
+    // that pass into `mid`, then PostBloom's into `dst` (rm_post_chain_batch),
+    // main.cpp:209-214 for every view at once.
+    bool drawBatch(const std::uint32_t* src, std::uint32_t* dst, int n) {
+        if (!loaded_) return fail("rm::PostShader: not loaded (ShaderLoader::loadFromFile(\"post.frag\", ...))");
+        fail("");  // (clear: a failure below is the library's message)
+        return rm_post_frag_batch(ctx(), (int)resolution_.x, (int)resolution_.y, n, sample_, tonemap_, src, dst) == RM_OK;
+    }
+    bool drawChainBatch(const std::uint32_t* src, std::uint32_t* mid, std::uint32_t* dst, int n) {
+        if (!loaded_) return fail("rm::PostShader: not loaded (ShaderLoader::loadFromFile(\"post.frag\", ...))");
+        fail("");
+        return rm_post_chain_batch(ctx(), (int)resolution_.x, (int)resolution_.y, n, sample_, tonemap_, src, mid, dst) ==
+               RM_OK;
+    }
 
 private:
     bool unknown(const char* name) { return fail(std::string("rm::PostShader: post.frag has no uniform ") + name); }
@@ -351,6 +367,12 @@ public:
             resolution_.x != (float)src.width() || resolution_.y != (float)src.height())
             return false;
         return rm_bloom(pass_.ctx(), src.width(), src.height(), src.textureRGBA8(), dst.textureRGBA8()) == RM_OK;
+    }
+    // apply() over n frames of init()'s resolution packed one after the other in
+    // device memory, such as a view batch's (rm_bloom_batch): view v of `dst` is
+    // apply() of view v of `src`
+    bool applyBatch(const uint32_t* src, uint32_t* dst, int n) {
+        return rm_bloom_batch(pass_.ctx(), (int)resolution_.x, (int)resolution_.y, n, src, dst) == RM_OK;
     }
 
 private:

@@ -37,7 +37,9 @@ EXPORTS = ("rm_create", "rm_destroy", "rm_load_scene", "rm_set_uniform1f", "rm_s
            "rm_resolution_cache_info", "rm_certified_steps", "rm_reflection_cleared_steps",
            "rm_near_sky_steps",
            "rm_batch_bytes", "rm_render_batch", "rm_render_batch_rgba8",
-           "rm_batch_aa_scratch_bytes", "rm_refine_batch_rgba8", "rm_render_batch_aa_rgba8")
+           "rm_batch_aa_scratch_bytes", "rm_refine_batch_rgba8", "rm_render_batch_aa_rgba8",
+           "rm_post_batch_plan", "rm_set_post_batch_scratch_limit", "rm_post_frag_batch", "rm_bloom_batch",
+           "rm_post_chain_batch")
 
 # include/rm.h RM_ABI_VERSION: the struct layouts below
 ABI_VERSION = 3
@@ -104,6 +106,20 @@ class RmView(ctypes.Structure):
     _fields_ = [("pos", ctypes.c_float * 3), ("mouse", ctypes.c_float * 2), ("time", ctypes.c_float),
                 ("offset", ctypes.c_float * 2)]
 
+
+class RmPostBatchPlan(ctypes.Structure):
+    """include/rm.h struct rm_post_batch_plan."""
+    _fields_ = [("per_view_bytes", ctypes.c_int64), ("shared_bytes", ctypes.c_int64),
+                ("group_views", ctypes.c_int32), ("groups", ctypes.c_int32), ("scratch_bytes", ctypes.c_int64),
+                ("launches", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+    def as_dict(self):
+        return dict(per_view_bytes=int(self.per_view_bytes), shared_bytes=int(self.shared_bytes),
+                    group_views=int(self.group_views), groups=int(self.groups),
+                    scratch_bytes=int(self.scratch_bytes), launches=int(self.launches))
+
+
+POST_BATCH_SCRATCH_DEFAULT = 512 << 20  # include/rm.h RM_POST_BATCH_SCRATCH_DEFAULT
 
 RAY_STATUS = {0: "miss", 1: "hit", 2: "exhausted"}  # include/rm.h RM_RAY_*
 
@@ -209,6 +225,11 @@ def lib() -> ctypes.CDLL:
                                    c.POINTER(RmAaStats)], c.c_int),
         "rm_render_batch_aa_rgba8": ([vp, c.c_int, c.c_int, vp, c.c_int, c.POINTER(RmAaParams), vp, vp, vp,
                                       c.POINTER(RmAaStats)], c.c_int),
+        "rm_post_batch_plan": ([c.c_int, c.c_int, c.c_int, c.c_int64, c.POINTER(RmPostBatchPlan)], c.c_int),
+        "rm_set_post_batch_scratch_limit": ([vp, c.c_int64], c.c_int),
+        "rm_post_frag_batch": ([vp, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, vp, vp], c.c_int),
+        "rm_bloom_batch": ([vp, c.c_int, c.c_int, c.c_int, vp, vp], c.c_int),
+        "rm_post_chain_batch": ([vp, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, vp, vp, vp], c.c_int),
         "rm_shade_rays": ([vp, vp, c.c_int, vp, c.c_int64, c.POINTER(RmShadeParams), vp, vp, c.POINTER(RmStats)],
                           c.c_int),
         "rm_sharded_layout": ([c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.POINTER(RmShardLayout)], c.c_int),

@@ -514,7 +514,53 @@ class Renderer:
                   self._ctx)
         return mid, out
 
-    SCENE_FORMS = {"exact": 0, "probe": 1, "probe_nb1": 2}  # rm.h rm_form
+    # --- the post passes over a batch of frames (rm_post_chain_batch) ---
+    def _post_batch_bufs(self, frames8, *others):
+        """frames8 [n, H, W] and the targets (allocated like it where None) -> n, H, W, targets."""
+        torch = _torch()
+        n, H, W = frames8.shape
+        bufs = [torch.empty_like(frames8) if t is None else t for t in others]
+        for t in (frames8, *bufs):
+            _check_out(t, n * H * W)
+        return n, H, W, bufs
+
+    def post_frag_batch(self, frames8, sample="fxaa", tonemap="none", out=None):
+        """post_frag of every frame of an [n, H, W] RGBA8 (int32 words) device
+        batch in one launch (rm_post_frag_batch): out[v] is byte for byte
+        post_frag(frames8[v]) with the same sample and tonemap."""
+        s, t = self._post_choice(sample, tonemap)
+        n, H, W, (out,) = self._post_batch_bufs(frames8, out)
+        check(lib().rm_post_frag_batch(self._ctx, W, H, n, s, t, self._ptr(frames8), self._ptr(out)), self._ctx)
+        return out
+
+    def bloom_batch(self, frames8, out=None):
+        """bloom of every frame of an [n, H, W] RGBA8 device batch
+        (rm_bloom_batch): out[v] is byte for byte bloom(frames8[v]).  The
+        launches do not grow with n, but for the groups the scratch limit
+        makes (post_batch_plan, set_post_batch_scratch_limit)."""
+        n, H, W, (out,) = self._post_batch_bufs(frames8, out)
+        check(lib().rm_bloom_batch(self._ctx, W, H, n, self._ptr(frames8), self._ptr(out)), self._ctx)
+        return out
+
+    def post_chain_batch(self, frames8, mid=None, out=None, sample="fxaa", tonemap="none"):
+        """post_chain of every frame of an [n, H, W] RGBA8 device batch, such
+        as render_batch's or render_batch_aa's (rm_post_chain_batch): returns
+        (mid, out), whose view v is byte for byte post_chain(frames8[v]) with
+        the same sample and tonemap.  frames8, mid and out must not overlap."""
+        s, t = self._post_choice(sample, tonemap)
+        n, H, W, (mid, out) = self._post_batch_bufs(frames8, mid, out)
+        check(lib().rm_post_chain_batch(self._ctx, W, H, n, s, t, self._ptr(frames8), self._ptr(mid),
+                                        self._ptr(out)), self._ctx)
+        return mid, out
+
+    def set_post_batch_scratch_limit(self, nbytes: int) -> None:
+        """The most bloom scratch a batched bloom of this renderer asks for
+        (rm_set_post_batch_scratch_limit); 0 restores the default,
+        POST_BATCH_SCRATCH_DEFAULT (512 MiB).  A batch whose views need more
+        runs in groups (post_batch_plan)."""
+        check(lib().rm_set_post_batch_scratch_limit(self._ctx, int(nbytes)), self._ctx)
+
+    SCENE_FORMS ={"exact": 0, "probe": 1, "probe_nb1": 2}  # rm.h rm_form
 
     def scene_eval(self, points, material: bool = False, form: str = "exact", aux: bool = False):
         """sceneSDF(p) of the loaded scene at points [n, 3] (host, numpy):
@@ -795,6 +841,16 @@ def batch_aa_scratch_bytes(W: int, H: int, n: int) -> int:
     b = ctypes.c_int64(0)
     check(lib().rm_batch_aa_scratch_bytes(int(W), int(H), int(n), ctypes.byref(b)))
     return int(b.value)
+
+
+def post_batch_plan(W: int, H: int, n: int, limit: int = 0) -> dict:
+    """rm_post_batch_plan: how post_chain_batch of n frames of W x H uses the
+    renderer's bloom scratch under a limit of `limit` bytes (0: the default) --
+    dict(per_view_bytes, shared_bytes, group_views, groups, scratch_bytes,
+    launches); RmError where the size rule refuses them.  No GPU."""
+    p = _lib.RmPostBatchPlan()
+    check(lib().rm_post_batch_plan(int(W), int(H), int(n), int(limit), ctypes.byref(p)))
+    return p.as_dict()
 
 
 def pack_views(views):

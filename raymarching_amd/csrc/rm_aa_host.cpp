@@ -14,7 +14,7 @@ using namespace rmhost;
 namespace {
 
 // The queue for a W x H frame on the context's stream.  One buffer per context
-// (bloom's rule, rm_capi.cpp bloom_scratch): a refine on another stream than
+// (bloom's rule, rm_post_batch_host.cpp bloom_scratch): a refine on another stream than
 // the last one first waits, on the device, for that one, marked when the
 // context left its stream (rm_ctx_streams.cpp set_stream).
 rm_status aa_scratch(rm_ctx *ctx, int W, int H) {

@@ -647,32 +647,6 @@ rm_status rm_fxaa(rm_ctx *ctx, int W, int H, const uint32_t *in, uint32_t *out) 
     });
 }
 
-// bloom's scratch (mip levels, run tables, polynomials) for W x H; whether its
-// run tables can be reused (the last bloom of this context had the same size
-// and stream: same buffer)
-static rm_status bloom_scratch(rm_ctx *ctx, const rm::BloomPlan &plan, int W, int H, bool &cached) {
-    if (ctx->bloom_ev && ctx->bloom_stream != ctx->stream)  // the last bloom ran on another stream
-        RM_HIP(hipStreamWaitEvent(ctx->stream, ctx->bloom_ev, 0));
-    if (plan.texels > ctx->mips_texels) {
-        if (ctx->mips) RM_HIP(hipFree(ctx->mips));
-        ctx->mips = nullptr;
-        ctx->mips_texels = 0;
-        ctx->bloom_runs_w = 0;
-        RM_HIP(hipMalloc(&ctx->mips, plan.texels * sizeof(uint32_t)));
-        ctx->mips_texels = plan.texels;
-    }
-    cached = ctx->bloom_runs_w == W && ctx->bloom_runs_h == H && ctx->bloom_runs_stream == ctx->stream;
-    ctx->bloom_runs_w = 0;
-    return RM_OK;
-}
-static void bloom_done(rm_ctx *ctx, int W, int H) {
-    ctx->bloom_stream = ctx->stream;
-    ctx->bloom_pending = true;
-    ctx->bloom_runs_w = W;
-    ctx->bloom_runs_h = H;
-    ctx->bloom_runs_stream = ctx->stream;
-}
-
 rm_status rm_bloom(rm_ctx *ctx, int W, int H, const uint32_t *in, uint32_t *out) {
     if (!ctx) return RM_ERR_INVALID_ARGUMENT;
     if (!in || !out || W <= 0 || H <= 0 || in == out)
@@ -683,7 +657,7 @@ rm_status rm_bloom(rm_ctx *ctx, int W, int H, const uint32_t *in, uint32_t *out)
     rm::TraceRange range("rm_bloom");
     const rm::BloomPlan plan = rm::bloom_plan(W, H);
     bool cached = false;
-    if (rm_status st = bloom_scratch(ctx, plan, W, H, cached)) return st;
+    if (rm_status st = bloom_scratch(ctx, plan.texels, W, H, cached)) return st;
     hipError_t e = rm::launch_bloom(in, out, ctx->mips, plan, ctx->stream, cached);
     if (e != hipSuccess) return hip_fail(ctx, e, "bloom launch");
     bloom_done(ctx, W, H);
@@ -703,7 +677,7 @@ rm_status rm_post_chain(rm_ctx *ctx, int W, int H, const uint32_t *in, uint32_t 
     rm::TraceRange range("rm_post_chain");
     const rm::BloomPlan plan = rm::bloom_plan(W, H);
     bool cached = false;
-    if (rm_status st = bloom_scratch(ctx, plan, W, H, cached)) return st;
+    if (rm_status st = bloom_scratch(ctx, plan.texels, W, H, cached)) return st;
     // main.cpp:209-214: FXAA into postTexture, its mip chain, bloom of it
     // (the mips from FXAA's registers measured slower)
     hipError_t e = rm::launch_fxaa(in, mid, W, H, ctx->stream);
@@ -758,7 +732,7 @@ rm_status rm_post_chain_ex(rm_ctx *ctx, int W, int H, int sample, int tonemap, c
     rm::TraceRange range("rm_post_chain_ex");
     const rm::BloomPlan plan = rm::bloom_plan(W, H);
     bool cached = false;
-    if (rm_status st = bloom_scratch(ctx, plan, W, H, cached)) return st;
+    if (rm_status st = bloom_scratch(ctx, plan.texels, W, H, cached)) return st;
     // main.cpp:209-214 with the edited post.frag: the pass into postTexture, bloom of it
     hipError_t e = rm::launch_post_frag(in, mid, W, H, sample, tonemap, ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "post chain: post_frag launch");

@@ -76,6 +76,9 @@ struct rm_ctx {
     hipEvent_t bloom_ev = nullptr;
     hipStream_t bloom_stream = nullptr;
     bool bloom_pending = false;  // a bloom ran on bloom_stream since bloom_ev was last recorded
+    // rm_set_post_batch_scratch_limit: the most of `mips` a batched bloom may ask for (0: the default,
+    // rm_post_batch_plan.h); the batch's views go through the buffer in groups that fit
+    int64_t post_batch_limit = 0;
     // adaptive supersampling's queue (rm_aa.h: the count's line, then a word per
     // pixel): one per context, grown on demand, with bloom's stream rule -- aa_ev
     // is recorded when the context leaves the stream of its last refine, and a
@@ -254,5 +257,13 @@ rm_status render_any(rm_ctx *ctx, int W, int H, int band, int nshards, int shard
 rm_status batch_records(rm_ctx *ctx, int W, int H, const rm_view *views, int n, rm::FrameConst &F, const void *&rec_d);
 rm_status batch_launch(rm_ctx *ctx, const rm::FrameConst &F, const void *rec_d, int n, void *out, bool rgba8,
                        rm_stats *stats);
+
+// ---- rm_post_batch_host.cpp
+// bloom's scratch (ctx->mips: mip levels, run tables, polynomials) holds at least `words` on the context's stream,
+// for rm_bloom, the post chains and their batch forms alike; `cached`: its run tables are W x H's already (the
+// last bloom of this context had the same size and stream, and the buffer is the same).  bloom_done: a bloom of
+// W x H was enqueued on the stream, its run tables at bloom_plan(W, H)'s offsets
+rm_status bloom_scratch(rm_ctx *ctx, size_t words, int W, int H, bool &cached);
+void bloom_done(rm_ctx *ctx, int W, int H);
 
 }  // namespace rmhost

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rm_bloom_plan.h"
 #include "rm_render_direct.h"
 
 namespace rm {
@@ -91,24 +92,23 @@ hipError_t launch_wire_decode_parts(const WireParts& parts, int W, uint32_t* fra
 hipError_t launch_scatter_part(const uint32_t* rows, int n, int W, int cycle, int offset, int run, uint32_t* frame,
                                hipStream_t s);
 
-// bloom.frag's textureLod level pair and the mip levels 1..d2 it needs,
-// packed one after the other in a scratch buffer of `texels` 32-bit words
-struct BloomPlan {
-    float lod = 0.0f, fr = 0.0f;
-    int d1 = 0, d2 = 0;
-    int w[40] = {}, h[40] = {};
-    size_t offset[40] = {}, texels = 0;
-    // lod > 0 (words from the buffer start): the base level's bilinear axes
-    // (per column, per row); per axis (d1 x, d1 y, d2 x, d2 y) the pixels' run
-    // entries, the runs' cell tuples and the run counts; per level the run-pair
-    // polynomials (rm_post.hip).  All but the polynomials depend on W x H only.
-    size_t base_ent[2] = {}, run_ent[4] = {}, run_tup[4] = {}, run_count = 0, poly_tab[2] = {};
-    int nruns[4] = {};  // most runs an axis can have
-};
-BloomPlan bloom_plan(int W, int H);
+// BloomPlan, bloom_plan(W, H): rm_bloom_plan.h (plain C++).
 // runs_cached: the buffer already holds this W x H's run tables, written on
 // this stream (only the mip levels and the polynomials are rebuilt)
 hipError_t launch_bloom(const uint32_t* in, uint32_t* out, uint32_t* mips, const BloomPlan& p, hipStream_t s,
                         bool runs_cached);
+// the run tables alone, at the plan's offsets in `mips` (rm_bloom_runs_kernel; lod > 0)
+hipError_t launch_bloom_runs(uint32_t* mips, const BloomPlan& p, hipStream_t s);
+
+// rm_post_batch.hip: the post passes over n frames of W x H packed one after
+// the other.  View v's frame is at in / out + v * W * H.
+hipError_t launch_post_frag_batch(const uint32_t* in, uint32_t* out, int W, int H, int n, int sample, int tonemap,
+                                  hipStream_t s);
+// `tables`: the run tables at the plan's offsets, already written on this
+// stream (lod > 0); view v's levels and polynomials at views + v * L.view_words
+// (rm_post_batch_plan.h view_layout)
+struct PostBatchViewLayout;
+hipError_t launch_bloom_batch(const uint32_t* in, uint32_t* out, int n, uint32_t* tables, uint32_t* views,
+                              const BloomPlan& p, const PostBatchViewLayout& L, hipStream_t s);
 
 }  // namespace rm
