@@ -21,8 +21,9 @@
 //          [--uniform name=v[,v...]]... [--pick X,Y] [--aa K[:threshold]]
 //          [--fisheye fov_deg] [--views FILE]
 // --views FILE renders one view batch instead of the frame loop
-// (rm::Shader::renderBatch -> rm_render_batch_rgba8): FILE holds one view per
-// line, px py pz mx my t [ox oy] (u_pos, u_mouse, u_time and an optional
+// (rm::Shader::renderBatchEx -> rm_render_batch_ex_rgba8: any scene, a .hip
+// scene plugin included, its --uniform values shared by the views): FILE holds
+// one view per line, px py pz mx my t [ox oy] (u_pos, u_mouse, u_time and an optional
 // sub-pixel offset), all rendered at --w x --h by one launch on one GPU.  With
 // --ppm NAME it writes NAME.0000.ppm, NAME.0001.ppm, ...; with --stats the JSON
 // line carries the launch's kernel_ms.  With --aa K[:threshold] the batch is
@@ -319,7 +320,7 @@ int main(int argc, char** argv) {
         const auto b0 = std::chrono::steady_clock::now();
         if (aa_samples ? !shader.renderBatchAA(w, h, views.data(), n, target, aa_samples, aa_threshold, nullptr,
                                                nullptr, &aa_st)
-                       : !shader.renderBatch(w, h, views.data(), n, target, stats ? &st : nullptr)) {
+                       : !shader.renderBatchEx(w, h, views.data(), n, nullptr, 0, target, stats ? &st : nullptr)) {
             std::fprintf(stderr, "--views failed: %s\n", shader.lastError().c_str());
             return 1;
         }

@@ -523,10 +523,12 @@ rm_status rm_render_aa_rgba8(rm_ctx *ctx, int W, int H, const rm_aa_params *para
  * no scene: RM_ERR_NO_SCENE; a scene plugin: RM_ERR_SCENE ("view batches:
  * built-in scenes only"), the target untouched; n = 0: RM_OK, nothing launched.
  * The device copy of the per-view constants is a scratch buffer of the context
- * (80 bytes per view for scenes S0 and T, 584 for O and OG) with the life and
+ * (80 bytes per view for scenes S0 and T, 584 for O and OG; a scene plugin
+ * through rm_render_batch_ex below: 592 + 16 * slots, the slots its uniforms
+ * take, one each and one per array element) with the life and
  * stream rule of rm_bloom's; several batches may be in flight on a stream at
  * once.
- *   Out of scope: scene plugins and per-view plugin uniforms; count_evals and
+ *   Out of scope: count_evals and
  * step maps per view; an adaptive or costliest-first order across views; views
  * of different sizes in one batch; device-resident view arrays; multi-GPU
  * batches.  (Adaptive supersampling of batched frames: rm_render_batch_aa_rgba8
@@ -542,6 +544,62 @@ rm_status rm_batch_bytes(int W, int H, int n, int rgba8, int64_t *frame_bytes, i
 rm_status rm_render_batch(rm_ctx *ctx, int W, int H, const rm_view *views, int n, float *out, rm_stats *stats);
 rm_status rm_render_batch_rgba8(rm_ctx *ctx, int W, int H, const rm_view *views, int n, uint32_t *out,
                                 rm_stats *stats);
+
+/* View batches of any scene, scene plugins included, with the scene's own
+ * uniforms set per view.  View v's frame is, byte for byte,
+ * what rm_render / rm_render_rgba8 writes after u_pos, u_mouse and u_time are
+ * set to the view's values and each uniform of the list is set to view v's
+ * values by the matching rm_set_uniform* call (rm_set_uniform{1..4}f,
+ * rm_set_uniformfv for the leading `count` elements of an array,
+ * rm_set_uniform1i for an int or a bool); every unlisted uniform has the
+ * context's current value, read at the call.  A non-zero `offset` means what it
+ * means for rm_render_batch.  The call neither reads the context's pose nor
+ * changes any of its uniform values: rm_get_uniformfv and rm_get_uniform1i answer
+ * after it what they answered before.  `uniforms` and every `values` are host
+ * pointers read during the call.  Target, staging, stats, stream, size rule and
+ * the rule for batches in flight are rm_render_batch's.
+ *   A built-in scene declares no uniforms: with n_uniforms == 0 the call is
+ * rm_render_batch[_rgba8]; with n_uniforms > 0 it returns
+ * RM_ERR_INVALID_ARGUMENT.  (rm_render_batch[_rgba8] and
+ * rm_render_batch_aa_rgba8 themselves keep refusing a scene plugin.)
+ *   A plugin's batch kernel is a second code object of the scene, compiled on
+ * the first batch call after the scene was loaded (cached by its text, as
+ * rm_load_scene caches), so that a scene never batched pays nothing; a call
+ * that must compile blocks for that long.  rm_batch_prepare compiles and loads
+ * it now: RM_OK at once for a built-in scene or when it is loaded already,
+ * RM_ERR_NO_SCENE without a scene, RM_ERR_SCENE for a plugin built with
+ * RM_PLUGIN_EVAL_ONLY.  rm_compile_scene_batch is rm_compile_scene for that
+ * code object (no GPU needed; a built-in scene: RM_OK with the compiled-in
+ * log; an RM_PLUGIN_EVAL_ONLY scene: RM_ERR_SCENE).
+ *   Errors, checked before any pointer is used, in this order, the target
+ * untouched: rm_render_batch's size rule and NULL `views` or `out`;
+ * n_uniforms < 0 or a NULL `uniforms` with n_uniforms > 0
+ * (RM_ERR_INVALID_ARGUMENT); no scene (RM_ERR_NO_SCENE); a plugin built with
+ * RM_PLUGIN_EVAL_ONLY (RM_ERR_SCENE); a built-in scene with n_uniforms > 0; an
+ * offset outside [-0.5, 0.5); then, per entry of the list, a NULL name, NULL
+ * values with n > 0, a uniform of the pass (u_time, ...), a name the scene does
+ * not declare, a name listed twice, components other than the declared type's
+ * (rm_last_error names the declared type), count < 1, count > 1 for a
+ * non-array, count above the declared length (all RM_ERR_INVALID_ARGUMENT).
+ * n = 0: RM_OK, nothing launched.
+ *   Out of scope: supersampling of a plugin batch; per-view max_steps or
+ * resolution; device-resident view or uniform arrays; count_evals and step maps
+ * per view; a dispatch order across views; multi-GPU batches. */
+typedef struct rm_view_uniform {
+    const char *name;    /* a uniform the loaded scene declares                        */
+    int32_t components;  /* 1..4, the declared type's (int, bool: 1)                   */
+    int32_t count;       /* elements given per view: 1 for a non-array; 1..N, the leading
+                            elements, for an array of N                                */
+    const void *values;  /* host; n * count * components 4-byte values, view-major:
+                            floats for a float-typed uniform, int32 for int and bool
+                            (non-zero: true)                                           */
+} rm_view_uniform;
+rm_status rm_render_batch_ex(rm_ctx *ctx, int W, int H, const rm_view *views, int n, const rm_view_uniform *uniforms,
+                             int n_uniforms, float *out, rm_stats *stats);
+rm_status rm_render_batch_ex_rgba8(rm_ctx *ctx, int W, int H, const rm_view *views, int n,
+                                   const rm_view_uniform *uniforms, int n_uniforms, uint32_t *out, rm_stats *stats);
+rm_status rm_batch_prepare(rm_ctx *ctx);
+rm_status rm_compile_scene_batch(const char *file_name, char *log, size_t log_size);
 
 /* Adaptive supersampling of a view batch: n antialiased RGBA8 frames from one
  * call -- the batch launch, then detect, plan and refine launches over all the

@@ -142,6 +142,23 @@ public:
     bool renderBatch(int w, int h, const rm_view* views, int n, float* out, rm_stats* stats = nullptr) {
         return ctx_ && rm_render_batch(ctx_, w, h, views, n, out, stats) == RM_OK;
     }
+    // rm.h rm_render_batch_ex[_rgba8]: renderBatch for any scene, a scene plugin
+    // included, with uniforms the scene declares set per view -- view v's frame
+    // is what setUniform(pose) + setUniform of view v's values of every listed
+    // uniform + RenderTexture::draw gives; an unlisted uniform keeps the value
+    // set on the shader, and the shader's own values do not change.  A plugin's
+    // batch kernel is compiled on the first call after loadFromFile unless
+    // batchPrepare did it before.  With a built-in scene: renderBatch, and a
+    // non-empty list fails.
+    bool renderBatchEx(int w, int h, const rm_view* views, int n, const rm_view_uniform* uniforms, int nUniforms,
+                       std::uint32_t* out, rm_stats* stats = nullptr) {
+        return ctx_ && rm_render_batch_ex_rgba8(ctx_, w, h, views, n, uniforms, nUniforms, out, stats) == RM_OK;
+    }
+    bool renderBatchEx(int w, int h, const rm_view* views, int n, const rm_view_uniform* uniforms, int nUniforms,
+                       float* out, rm_stats* stats = nullptr) {
+        return ctx_ && rm_render_batch_ex(ctx_, w, h, views, n, uniforms, nUniforms, out, stats) == RM_OK;
+    }
+    bool batchPrepare() { return ctx_ && rm_batch_prepare(ctx_) == RM_OK; }
     // rm.h rm_render_batch_aa_rgba8: renderBatch's RGBA8 frames with every view's
     // edge pixels supersampled, view v's frame what setUniform(pose) +
     // RenderTexture::drawAA(shader, samples, threshold) gives.  mask (n * w * h

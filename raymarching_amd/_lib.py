@@ -39,7 +39,8 @@ EXPORTS = ("rm_create", "rm_destroy", "rm_load_scene", "rm_set_uniform1f", "rm_s
            "rm_batch_bytes", "rm_render_batch", "rm_render_batch_rgba8",
            "rm_batch_aa_scratch_bytes", "rm_refine_batch_rgba8", "rm_render_batch_aa_rgba8",
            "rm_post_batch_plan", "rm_set_post_batch_scratch_limit", "rm_post_frag_batch", "rm_bloom_batch",
-           "rm_post_chain_batch")
+           "rm_post_chain_batch",
+           "rm_render_batch_ex", "rm_render_batch_ex_rgba8", "rm_batch_prepare", "rm_compile_scene_batch")
 
 # include/rm.h RM_ABI_VERSION: the struct layouts below
 ABI_VERSION = 3
@@ -105,6 +106,12 @@ class RmView(ctypes.Structure):
     """include/rm.h rm_view: one view of a batch (rm_render_batch*)."""
     _fields_ = [("pos", ctypes.c_float * 3), ("mouse", ctypes.c_float * 2), ("time", ctypes.c_float),
                 ("offset", ctypes.c_float * 2)]
+
+
+class RmViewUniform(ctypes.Structure):
+    """include/rm.h rm_view_uniform: one uniform of the loaded scene, set per view (rm_render_batch_ex*)."""
+    _fields_ = [("name", ctypes.c_char_p), ("components", ctypes.c_int32), ("count", ctypes.c_int32),
+                ("values", ctypes.c_void_p)]
 
 
 class RmPostBatchPlan(ctypes.Structure):
@@ -209,6 +216,7 @@ def lib() -> ctypes.CDLL:
         "rm_render_cycle_rows_wire": ([vp, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, vp, vp, vp,
                                        c.POINTER(RmStats)], c.c_int),
         "rm_compile_scene": ([cp, vp, c.c_size_t], c.c_int),
+        "rm_compile_scene_batch": ([cp, vp, c.c_size_t], c.c_int),
         "rm_scene_eval": ([vp, vp, c.c_int64, vp, vp], c.c_int),
         "rm_scene_eval_form": ([vp, vp, c.c_int64, c.c_int, vp, vp, vp], c.c_int),
         "rm_cast_rays": ([vp, vp, c.c_int, vp, c.c_int64, c.c_int, c.POINTER(RmRayHits), c.POINTER(RmStats)], c.c_int),
@@ -220,6 +228,9 @@ def lib() -> ctypes.CDLL:
         "rm_batch_bytes": ([c.c_int, c.c_int, c.c_int, c.c_int, c.POINTER(c.c_int64), c.POINTER(c.c_int64)], c.c_int),
         "rm_render_batch": ([vp, c.c_int, c.c_int, vp, c.c_int, vp, c.POINTER(RmStats)], c.c_int),
         "rm_render_batch_rgba8": ([vp, c.c_int, c.c_int, vp, c.c_int, vp, c.POINTER(RmStats)], c.c_int),
+        "rm_render_batch_ex": ([vp, c.c_int, c.c_int, vp, c.c_int, vp, c.c_int, vp, c.POINTER(RmStats)], c.c_int),
+        "rm_render_batch_ex_rgba8": ([vp, c.c_int, c.c_int, vp, c.c_int, vp, c.c_int, vp, c.POINTER(RmStats)], c.c_int),
+        "rm_batch_prepare": ([vp], c.c_int),
         "rm_batch_aa_scratch_bytes": ([c.c_int, c.c_int, c.c_int, c.POINTER(c.c_int64)], c.c_int),
         "rm_refine_batch_rgba8": ([vp, c.c_int, c.c_int, vp, c.c_int, c.POINTER(RmAaParams), vp, vp, vp,
                                    c.POINTER(RmAaStats)], c.c_int),

@@ -739,6 +739,65 @@ class Renderer:
                  ctypes.byref(s) if stats else None), self._ctx)
         return (out, self._stats(s)) if stats else out
 
+    def render_batch_ex(self, W: int, H: int, views, uniforms=None, out=None, rgba8: bool = True,
+                        stats: bool = False):
+        """render_batch for any scene, a scene plugin included, with the scene's
+        own uniforms set per view (rm_render_batch_ex[_rgba8]).
+        uniforms: a dict from the name of a uniform the loaded scene declares to
+        an array of shape [n] (a float, an int or a bool per view),
+        [n, components] (a vecN per view; for an array of floats, its leading
+        elements) or [n, count, components] (the leading `count` elements of an
+        array uniform).  An int or bool uniform, by its declared type, takes
+        integers (non-zero: true), every other floats.  View v's frame is byte
+        for byte what set_pose + set_uniform of view v's values + render_rgba8 /
+        render gives; an unlisted uniform has the renderer's current value.  The
+        renderer's own pose and uniform values are neither read nor changed.
+        A plugin's batch kernel is compiled on the first call after load_scene
+        (batch_prepare compiles it ahead).  For a built-in scene: render_batch,
+        and a non-empty `uniforms` raises.  views, out, rgba8, stats: as
+        render_batch."""
+        import numpy as np
+        v = pack_views(views)
+        n = len(v)
+        infos = {u.name.decode(): u for u in self._uniform_infos()}
+        entries, keep = [], []
+        for name, values in (uniforms or {}).items():
+            info = infos.get(name)
+            ints = info is not None and _lib.UNIFORM_TYPES[info.type] in ("int", "bool")
+            a = np.ascontiguousarray(values.cpu().numpy() if hasattr(values, "cpu") else values,
+                                     np.int32 if ints else np.float32)
+            if a.ndim == 1:
+                a = a.reshape(-1, 1, 1)
+            elif a.ndim == 2 and info is not None and info.count and info.components == 1:
+                a = a.reshape(a.shape[0], a.shape[1], 1)
+            elif a.ndim == 2:
+                a = a.reshape(a.shape[0], 1, a.shape[1])
+            if a.ndim != 3 or a.shape[0] != n:
+                raise ValueError(f"render_batch_ex: uniform {name!r} needs [n], [n, components] or "
+                                 f"[n, count, components] values for n = {n} views")
+            keep.append((name.encode(), a))
+            entries.append(_lib.RmViewUniform(keep[-1][0], int(a.shape[2]), int(a.shape[1]),
+                                              ctypes.c_void_p(a.ctypes.data)))
+        arr = (_lib.RmViewUniform * max(1, len(entries)))(*entries)
+        per_px = 1 if rgba8 else 4
+        if out is None:
+            torch = _torch()
+            out = torch.empty((n, H, W) if rgba8 else (n, H, W, 4), dtype=torch.int32 if rgba8 else torch.float32,
+                              device=f"cuda:{self.device}")
+        _check_out(out, n * H * W * per_px)
+        s = RmStats()
+        fn = lib().rm_render_batch_ex_rgba8 if rgba8 else lib().rm_render_batch_ex
+        check(fn(self._ctx, int(W), int(H), ctypes.c_void_p(v.ctypes.data), n,
+                 ctypes.cast(arr, ctypes.c_void_p) if entries else None, len(entries), self._ptr(out),
+                 ctypes.byref(s) if stats else None), self._ctx)
+        return (out, self._stats(s)) if stats else out
+
+    def batch_prepare(self) -> None:
+        """rm_batch_prepare: compile and load the loaded plugin's batch kernel
+        now, not inside the first render_batch_ex (nothing to do for a built-in
+        scene or once it is loaded)."""
+        check(lib().rm_batch_prepare(self._ctx), self._ctx)
+
     # --- adaptive supersampling (rm_render_aa_rgba8, rm_refine_rgba8) -----
     def _aa(self, fn, W, H, samples, threshold, frame8, mask, stats):
         """frame8: [H, W] RGBA8 words, a device tensor or a numpy array (staged);
@@ -1024,6 +1083,18 @@ def compile_scene(file_name: str):
     Returns (ok, log); a missing file or #include raises RmError."""
     buf = ctypes.create_string_buffer(1 << 16)
     st = lib().rm_compile_scene(file_name.encode(), ctypes.cast(buf, ctypes.c_void_p), len(buf))
+    log = buf.value.decode(errors="replace")
+    if st == _lib.STATUS_CODES["RM_ERR_FILE"]:
+        raise _lib.RmError(st, log)
+    return st == 0, log
+
+
+def compile_scene_batch(file_name: str):
+    """rm_compile_scene_batch: compile_scene for the batch form of a plugin's
+    code object (Renderer.render_batch_ex's kernel).  (False, log) for a scene
+    that defines RM_PLUGIN_EVAL_ONLY."""
+    buf = ctypes.create_string_buffer(1 << 16)
+    st = lib().rm_compile_scene_batch(file_name.encode(), ctypes.cast(buf, ctypes.c_void_p), len(buf))
     log = buf.value.decode(errors="replace")
     if st == _lib.STATUS_CODES["RM_ERR_FILE"]:
         raise _lib.RmError(st, log)

@@ -150,6 +150,9 @@ rm_status rm_load_scene(rm_ctx *ctx, const char *file_name) {
             RM_HIP(hipStreamSynchronize(ctx->stream));
             hipError_t e = rmplugin::load(code, uniforms.slots, ctx->plugin);
             if (e != hipSuccess) return hip_fail(ctx, e, "scene plugin module load");
+            // (what the batch form is compiled from on its first use, rm_render_batch_ex)
+            ctx->plugin.src = src;
+            ctx->plugin.file = file;
         }
     } else if (sc < 0) {
         std::string err = "ShaderLoader: can't load file \"" + file + "\"";
@@ -804,7 +807,8 @@ rm_status rm_scene_eval_form(rm_ctx *ctx, const float *points, int64_t n, int fo
     return scene_eval_form(ctx, points, n, form, dist, material, aux, "rm_scene_eval_form");
 }
 
-rm_status rm_compile_scene(const char *file_name, char *log, size_t log_size) {
+// rm_compile_scene; batch: the batch form of the code object (rm_compile_scene_batch)
+static rm_status compile_scene(const char *file_name, char *log, size_t log_size, bool batch) {
     if (!file_name) return RM_ERR_INVALID_ARGUMENT;
     std::string src, err, clog;
     int sc = -1;
@@ -816,7 +820,7 @@ rm_status rm_compile_scene(const char *file_name, char *log, size_t log_size) {
     } else {
         rmplugin::Code code;
         rmuniform::Table uniforms;
-        if (!rmplugin::compile(src, file_name, code, clog, uniforms)) st = RM_ERR_SCENE;
+        if (!rmplugin::compile(src, file_name, code, clog, uniforms, batch)) st = RM_ERR_SCENE;
     }
     if (log && log_size > 0) {
         size_t k = clog.size() < log_size - 1 ? clog.size() : log_size - 1;
@@ -824,6 +828,14 @@ rm_status rm_compile_scene(const char *file_name, char *log, size_t log_size) {
         log[k] = '\0';
     }
     return st;
+}
+
+rm_status rm_compile_scene(const char *file_name, char *log, size_t log_size) {
+    return compile_scene(file_name, log, log_size, false);
+}
+
+rm_status rm_compile_scene_batch(const char *file_name, char *log, size_t log_size) {
+    return compile_scene(file_name, log, log_size, true);
 }
 
 int rm_abi_version(void) { return RM_ABI_VERSION; }

@@ -254,9 +254,29 @@ rm_status render_any(rm_ctx *ctx, int W, int H, int band, int nshards, int shard
 // a view batch's shared constants F (W x H, row-major) and the upload of its n per-view records (rm_batch.h) on
 // the context's stream, then its one launch into the device pointer `out`: rm_render_batch's two halves, which
 // rm_batch_aa_host.cpp calls too (a refine alone takes the records without the launch)
-rm_status batch_records(rm_ctx *ctx, int W, int H, const rm_view *views, int n, rm::FrameConst &F, const void *&rec_d);
+// (a scene plugin's records, rm_plugin_host.h batch_record_stride: the view's whole FrameConst, then its uniform
+// block, view v's at blocks + v * 4 * slots words -- rm_plugin_batch_pack.h's; built-in scenes take none)
+rm_status batch_records(rm_ctx *ctx, int W, int H, const rm_view *views, int n, rm::FrameConst &F, const void *&rec_d,
+                        const uint32_t *blocks = nullptr);
 rm_status batch_launch(rm_ctx *ctx, const rm::FrameConst &F, const void *rec_d, int n, void *out, bool rgba8,
                        rm_stats *stats);
+// rm_render_batch[_rgba8] (ex null: a scene plugin is refused) and rm_render_batch_ex[_rgba8]: the checks in
+// include/rm.h's order, the staging of a host target, the records and the launch
+struct BatchEx {
+    const rm_view_uniform *uniforms;
+    int n_uniforms;
+};
+rm_status batch_run(rm_ctx *ctx, int W, int H, const rm_view *views, int n, void *out, bool rgba8, rm_stats *stats,
+                    const BatchEx *ex);
+
+// ---- rm_plugin_batch_host.cpp
+// what rm_render_batch_ex asks of the loaded scene before any view is looked at: a plugin must have render kernels,
+// a built-in scene takes no uniforms
+rm_status batch_ex_scene(rm_ctx *ctx, const BatchEx &ex);
+// a plugin's per-view uniform blocks from the list (RM_ERR_INVALID_ARGUMENT with the list's fault in rm_last_error)
+rm_status batch_ex_blocks(rm_ctx *ctx, const BatchEx &ex, int n, std::vector<uint32_t> &blocks);
+// the loaded plugin's batch kernel, compiled and loaded if it is not yet
+rm_status batch_ex_ready(rm_ctx *ctx);
 
 // ---- rm_post_batch_host.cpp
 // bloom's scratch (ctx->mips: mip levels, run tables, polynomials) holds at least `words` on the context's stream,

@@ -35,10 +35,36 @@ namespace glsl {
 // u_time stayed inside the loops, whose volatile asm statements LLVM must
 // assume to write memory, and the scene-O plugin evaluated two sin and two
 // cos, with two IEEE divisions, on every ray-step.)
+//
+// The batch form (#define RM_PLUGIN_BATCH at the head of the translation unit;
+// include/rm.h rm_render_batch_ex): the views of a batch differ
+// in these values, so they cannot be kernel arguments.  Each view has a record
+// in device memory -- its whole FrameConst, then at kUniformOffset its uniform
+// block: PluginArgsHead's layout -- and plugin_bytes() below is the address of
+// the record of the workgroup's view, blockIdx.z: the pointer in the kernel's
+// first argument plus blockIdx.z * kRecordStride, wave-uniform.  The memory is
+// read-only for the launch and is read through the constant address space too,
+// so the loads stay scalar and invariant, and hoist as the frame form's do.
 typedef const __attribute__((address_space(4))) FrameConst* KernargFrame;
-__device__ __forceinline__ KernargFrame plugin_frame() {
-    return (KernargFrame)__builtin_amdgcn_kernarg_segment_ptr();
+typedef const __attribute__((address_space(4))) char* KernargBytes;
+constexpr int kUniformOffset = (int)((sizeof(FrameConst) + 15) & ~(size_t)15);
+#ifdef RM_UNIFORM_SLOTS
+constexpr int kRecordStride = kUniformOffset + 16 * RM_UNIFORM_SLOTS;
+#else
+constexpr int kRecordStride = kUniformOffset;
+#endif
+// where the pass's uniforms and the scene's block are read from
+__device__ __forceinline__ KernargBytes plugin_bytes() {
+#ifdef RM_PLUGIN_BATCH
+    // (the kernel's first parameter, a pointer to the records)
+    typedef const __attribute__((address_space(4))) KernargBytes* KernargPointer;
+    const KernargBytes records = *(KernargPointer)__builtin_amdgcn_kernarg_segment_ptr();
+    return records + (size_t)blockIdx.z * (size_t)kRecordStride;
+#else
+    return (KernargBytes)__builtin_amdgcn_kernarg_segment_ptr();
+#endif
 }
+__device__ __forceinline__ KernargFrame plugin_frame() { return (KernargFrame)plugin_bytes(); }
 
 #ifdef RM_UNIFORM_SLOTS
 // The uniforms a scene declares itself (`uniform vec4 u_ball = ...;`,
@@ -54,19 +80,15 @@ struct PluginArgsHead {  // the kernels' first two parameters, as the kernel-arg
     FrameConst F;
     UniformBlock U;
 };
-constexpr int kUniformOffset = (int)((sizeof(FrameConst) + 15) & ~(size_t)15);
 static_assert(__builtin_offsetof(PluginArgsHead, U) == kUniformOffset && alignof(FrameConst) <= 16,
               "the uniform block follows the FrameConst in the kernel-argument segment");
 static_assert(RM_UNIFORM_SLOTS >= 1 && RM_UNIFORM_SLOTS <= 64, "rm_uniform_decl.h kMaxSlots");
 
-typedef const __attribute__((address_space(4))) char* KernargBytes;
 __device__ __forceinline__ float uniform_f(int byte) {
-    return *(const __attribute__((address_space(4))) float*)((KernargBytes)__builtin_amdgcn_kernarg_segment_ptr() +
-                                                             kUniformOffset + byte);
+    return *(const __attribute__((address_space(4))) float*)(plugin_bytes() + kUniformOffset + byte);
 }
 __device__ __forceinline__ int uniform_i(int byte) {
-    return *(const __attribute__((address_space(4))) int*)((KernargBytes)__builtin_amdgcn_kernarg_segment_ptr() +
-                                                           kUniformOffset + byte);
+    return *(const __attribute__((address_space(4))) int*)(plugin_bytes() + kUniformOffset + byte);
 }
 // a float / vec2 / vec3 / vec4 (of either library instance) at a byte offset of the block
 template <class V>

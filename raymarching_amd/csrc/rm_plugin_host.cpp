@@ -186,7 +186,8 @@ namespace {
 std::mutex g_mu;
 std::map<std::string, Code> g_cache;
 
-std::string translation_unit(const std::string& src, const std::string& file, const rmuniform::Table& uniforms) {
+std::string translation_unit(const std::string& src, const std::string& file, const rmuniform::Table& uniforms,
+                             bool batch) {
     std::string name;
     for (char c : file) {
         if (c == '"' || c == '\\') name += '\\';
@@ -216,6 +217,9 @@ std::string translation_unit(const std::string& src, const std::string& file, co
         head = "#define RM_UNIFORM_SLOTS " + std::to_string(uniforms.slots) + "\n";
         rmuniform::device_text(uniforms, defines, undefs);
     }
+    // the batch form is the frame form's text behind one #define: the same scene text in the same two instances
+    // under the same pragmas, so that a view's bytes are the frame kernels' (rm_plugin.h, rm_plugin_kernels.h)
+    if (batch) head = "#define RM_PLUGIN_BATCH 1\n" + head;
     return head + "#include \"rm_plugin.h\"\n" + defines +
            instance("namespace rm {\nnamespace glsl {\n", "}  // namespace glsl\n}  // namespace rm\n", "", "") +
            instance("namespace rm {\nnamespace glsl {\nnamespace probe {\n",
@@ -227,16 +231,25 @@ std::string translation_unit(const std::string& src, const std::string& file, co
 }  // namespace
 
 bool compile(const std::string& src, const std::string& file, Code& code, std::string& log,
-             rmuniform::Table& uniforms) {
+             rmuniform::Table& uniforms, bool batch) {
     std::string scene;
     if (!rmuniform::parse(src, file, uniforms, scene, log)) return false;
-    const std::string tu = translation_unit(scene, file, uniforms);
+    const std::string tu = translation_unit(scene, file, uniforms, batch);
     log.clear();
+    // debugging: the TU and its code object (a cached one too), the batch form's beside the frame form's
+    auto dump = [&](const Code& c) {
+        const char* dir = std::getenv("RM_PLUGIN_DUMP");
+        if (!dir) return;
+        const std::string stem = std::string(dir) + (batch ? "/plugin_batch" : "/plugin");
+        std::ofstream(stem + "_tu.hip") << tu;
+        std::ofstream(stem + ".co", std::ios::binary).write(c->data(), (std::streamsize)c->size());
+    };
     {
         std::lock_guard<std::mutex> g(g_mu);
         auto it = g_cache.find(tu);
         if (it != g_cache.end()) {
             code = it->second;
+            dump(code);
             return true;
         }
     }
@@ -270,11 +283,8 @@ bool compile(const std::string& src, const std::string& file, Code& code, std::s
     auto v = std::make_shared<std::vector<char>>(cs);
     hiprtcGetCode(prog, v->data());
     hiprtcDestroyProgram(&prog);
-    if (const char* dir = std::getenv("RM_PLUGIN_DUMP")) {  // debugging: the TU and its code object
-        std::ofstream(std::string(dir) + "/plugin_tu.hip") << tu;
-        std::ofstream(std::string(dir) + "/plugin.co", std::ios::binary).write(v->data(), (std::streamsize)cs);
-    }
     code = v;
+    dump(code);
     std::lock_guard<std::mutex> g(g_mu);
     g_cache[tu] = v;
     return true;
@@ -305,14 +315,50 @@ hipError_t load(const Code& code, int uniform_slots, Module& m) {
     }
     n.code = code;
     n.uniform_slots = uniform_slots;
-    unload(m);
+    unload(m);  // (the batch form of the scene before with it)
     m = n;
     return hipSuccess;
 }
 
 void unload(Module& m) {
+    if (m.batch_mod) (void)hipModuleUnload(m.batch_mod);
     if (m.mod) (void)hipModuleUnload(m.mod);
     m = Module();
+}
+
+bool batch_ready(Module& m, std::string& err, hipError_t& e) {
+    e = hipSuccess;
+    if (m.render_batch) return true;
+    Code code;
+    rmuniform::Table uniforms;
+    if (!compile(m.src, m.file, code, err, uniforms, true)) return false;
+    hipModule_t mod = nullptr;
+    e = hipModuleLoadData(&mod, code->data());
+    if (e == hipSuccess) {
+        e = hipModuleGetFunction(&m.render_batch, mod, "rm_plugin_render_batch");
+        if (e != hipSuccess) {
+            (void)hipModuleUnload(mod);
+            m.render_batch = nullptr;
+        }
+    }
+    if (e != hipSuccess) {
+        err = std::string("scene plugin batch module load: ") + hipGetErrorString(e);
+        return false;
+    }
+    m.batch_mod = mod;
+    return true;
+}
+
+hipError_t launch_render_batch(const Module& m, const void* records, int W, int H, int n, void* out, bool rgba8,
+                               hipStream_t s) {
+    if (!m.render_batch) return hipErrorInvalidDeviceFunction;
+    if (n <= 0) return hipSuccess;
+    const void* r = records;
+    void* o = out;
+    int r8 = rgba8 ? 1 : 0;
+    void* args[] = {&r, &o, &r8};
+    return hipModuleLaunchKernel(m.render_batch, (unsigned)((W + 7) / 8), (unsigned)((H + 7) / 8), (unsigned)n, 64, 1,
+                                 1, 0, s, args, nullptr);
 }
 
 hipError_t launch_render(const Module& m, const rm::FrameConst& F, const uint32_t* uniforms, void* out, bool rgba8,

@@ -31,8 +31,11 @@ std::string glsl_source(const std::string& src);
 // compiler sees the source with the declarations blanked, so two sources that
 // differ in a default value share a code object and nothing else.  On failure
 // `log` holds the diagnostics.
+// `batch`: the batch form of the translation unit (rm_plugin.h RM_PLUGIN_BATCH):
+// the same scene text and options, one kernel, rm_plugin_render_batch; a scene
+// that defines RM_PLUGIN_EVAL_ONLY has no such form and fails to compile.
 bool compile(const std::string& src, const std::string& file, Code& code, std::string& log,
-             rmuniform::Table& uniforms);
+             rmuniform::Table& uniforms, bool batch = false);
 
 struct Module {
     hipModule_t mod = nullptr;
@@ -44,10 +47,26 @@ struct Module {
     hipFunction_t shade = nullptr;         // rm_shade_rays' kernel; null for an RM_PLUGIN_EVAL_ONLY scene
     Code code;
     int uniform_slots = 0;  // > 0: the kernels take the uniform block as their second argument (rm_plugin.h)
+    // the batch form (rm_render_batch_ex): a code object and a module of its own, compiled from `src` and loaded
+    // by batch_ready on first use, dropped with the module (load, unload)
+    std::string src, file;  // the preprocessed scene source rm_load_scene compiled, and its file name
+    hipModule_t batch_mod = nullptr;
+    hipFunction_t render_batch = nullptr;
 };
 // on the current device; m keeps its old module on failure
 hipError_t load(const Code& code, int uniform_slots, Module& m);
 void unload(Module& m);
+// The batch form of m's scene, compiled (cached by text, as compile caches) and loaded on the current device; at
+// once if it is loaded already.  False with `err` set: `e` is hipSuccess if the compilation failed.
+bool batch_ready(Module& m, std::string& err, hipError_t& e);
+// bytes of one view's record: the FrameConst, then the uniform block at rm_plugin.h's kUniformOffset
+constexpr size_t kBatchUniformOffset = (sizeof(rm::FrameConst) + 15) & ~(size_t)15;
+static_assert(kBatchUniformOffset == 592, "include/rm.h states a plugin record's bytes");
+inline size_t batch_record_stride(int uniform_slots) { return kBatchUniformOffset + 16 * (size_t)uniform_slots; }
+// n views of W x H from `records` (device memory, n records of batch_record_stride(m.uniform_slots) bytes) into
+// the packed frames at `out`; hipErrorInvalidDeviceFunction before batch_ready
+hipError_t launch_render_batch(const Module& m, const void* records, int W, int H, int n, void* out, bool rgba8,
+                               hipStream_t s);
 // `uniforms`: the context's block of rmuniform::kBlockWords words, copied into
 // the kernel arguments by the launch call (its first m.uniform_slots slots)
 hipError_t launch_render(const Module& m, const rm::FrameConst& F, const uint32_t* uniforms, void* out, bool rgba8,

@@ -71,6 +71,28 @@ __device__ __forceinline__ void plugin_render_tile(const FrameConst& F, void* ou
     if constexpr (COUNT) store_tally(F, evals, cnt, x, j, lane);
 }
 }  // namespace rm
+#ifdef RM_PLUGIN_BATCH
+// The batch form of the translation unit (rm_plugin.h; include/rm.h rm_render_batch_ex) has this
+// kernel alone: one 8x8 wave tile of view blockIdx.z, by the timed kernel's own code, with F bound to the view's
+// record -- which the scene's functions read through rm_plugin.h's accessors, so `records` is named here only to
+// be the first parameter.  The pass's uniforms a scene may read, and the scene's own, are loaded at the top (as
+// RM_UNIFORM_PRELOAD's are in the frame form), so that their reads inside the march loops are copies of these.
+extern "C" __global__ __launch_bounds__(64) void rm_plugin_render_batch(const void* records, void* out, int rgba8) {
+    const rm::glsl::KernargFrame K = rm::glsl::plugin_frame();
+    asm volatile("" ::"s"(K->time), "s"(K->pos_x), "s"(K->pos_y), "s"(K->pos_z), "s"(K->mouse_x), "s"(K->mouse_y),
+                 "s"(K->res_x), "s"(K->res_y));
+    RM_UNIFORM_PRELOAD();
+    const rm::FrameConst& G = *(const rm::FrameConst*)K;
+    // what every record of a batch holds (rm_batch.h launch_batch_scene's rule, which rm_batch_host.cpp's
+    // records keep): no dispatch order, no tile durations, no accumulation -- said here so that those paths of
+    // plugin_render_tile are not compiled in
+    __builtin_assume(G.tile_order == nullptr);
+    __builtin_assume(G.tile_cost == nullptr);
+    __builtin_assume(G.accumulate == 0);
+    const size_t frame = (size_t)G.W * (size_t)G.H * (rgba8 ? sizeof(uint32_t) : sizeof(float4));
+    rm::plugin_render_tile<false>(G, static_cast<char*>(out) + (size_t)blockIdx.z * frame, rgba8, nullptr);
+}
+#else
 extern "C" __global__ __launch_bounds__(64) void rm_plugin_render(rm::FrameConst F, RM_UNIFORM_PARAM void* out,
                                                                   int rgba8, unsigned long long* evals) {
     RM_UNIFORM_PRELOAD();
@@ -89,8 +111,12 @@ extern "C" __global__ __launch_bounds__(64) void rm_plugin_shade(rm::FrameConst 
     RM_UNIFORM_PRELOAD();
     rm::shade_rays_one<rm::SCENE_PLUGIN, rm::SHADE_PER_LAUNCH, rm::SHADE_PER_LAUNCH>(F, Q);
 }
+#endif  // RM_PLUGIN_BATCH
+#elif defined(RM_PLUGIN_BATCH)
+#error "the scene defines RM_PLUGIN_EVAL_ONLY (no render kernel): it has no batch form"
 #endif
 
+#ifndef RM_PLUGIN_BATCH
 // sceneSDF(p) at explicit points (rm_scene_eval)
 extern "C" __global__ __launch_bounds__(256) void rm_plugin_eval(rm::FrameConst F, RM_UNIFORM_PARAM const float* pts,
                                                                  long long n, float* dist, float* mat) {
@@ -118,3 +144,4 @@ extern "C" __global__ __launch_bounds__(256) void rm_plugin_cast(rm::FrameConst 
     RM_UNIFORM_PRELOAD();
     rm::cast_rays_one<rm::SCENE_PLUGIN>(F, Q, inside);
 }
+#endif  // RM_PLUGIN_BATCH

@@ -194,6 +194,12 @@ void Table::defaults(uint32_t block[kBlockWords]) const {
         if (!d.count) std::memcpy(block + 4 * d.slot, d.def, sizeof(d.def));
 }
 
+bool is_pass_name(const std::string& name) {
+    for (const char* p : kPassNames)
+        if (name == p) return true;
+    return false;
+}
+
 std::string type_name(const Decl& d) {
     std::string s = d.type == kInt ? "int" : d.type == kBool ? "bool"
                     : d.components == 1 ? "float" : "vec" + std::to_string(d.components);

@@ -47,6 +47,9 @@ struct Table {
     void defaults(uint32_t block[kBlockWords]) const;
 };
 
+// a uniform of the pass itself (u_time, u_pos, ...: no scene may declare one)
+bool is_pass_name(const std::string& name);
+
 // the GLSL spelling of a declaration's type ("vec4", "float[8]"), for messages
 std::string type_name(const Decl& d);
 
