@@ -42,10 +42,11 @@
 // rm_shade_rays) as a ray image with the frame's vignette into RGBA8 words.
 // One GPU.
 // --aa K[:threshold] draws each frame with adaptive supersampling
-// (rm::RenderTexture::drawAA -> rm_render_aa_rgba8): K = 2, 4 or 8 samples at
+// (rm::RenderTexture::drawAAEx -> rm_render_aa_ex_rgba8: any scene, a .hip
+// scene plugin included): K = 2, 4 or 8 samples at
 // the pixels whose 3x3 neighbourhood spreads a colour channel by at least
-// threshold (0..255, default 32; 0: every pixel).  One GPU, the RGBA8 target,
-// built-in scenes; --stats then counts the base frame's, the detect and the
+// threshold (0..255, default 32; 0: every pixel).  One GPU, the RGBA8 target
+// (with --views: built-in scenes); --stats then counts the base frame's, the detect and the
 // refine kernel.
 // --uniform sets a uniform the scene declares itself (a scene plugin's
 // `uniform vec4 u_ball = ...;`, rm.h rm_load_scene) once the scene is loaded:
@@ -431,7 +432,7 @@ int main(int argc, char** argv) {
         // supersampling while the camera is still; one GPU)
         const bool drawn = sharded      ? shardedTexture.draw(stp)
                            : accumulate ? outputTexture.drawAccumulate(shader, stp)
-                           : aa_samples ? outputTexture.drawAA(shader, aa_samples, aa_threshold, stats ? &aa_st : nullptr)
+                           : aa_samples ? outputTexture.drawAAEx(shader, aa_samples, aa_threshold, stats ? &aa_st : nullptr)
                                         : outputTexture.draw(shader, stp);
         if (drawn && aa_samples && stats) st[0].kernel_ms = aa_st.base_ms + aa_st.detect_ms + aa_st.refine_ms;
         if (!drawn) {

@@ -470,9 +470,40 @@ rm_status rm_render_accumulate_rgba8(rm_ctx *ctx, int W, int H, uint32_t *accum,
  * built-in scenes only"), the frame untouched -- all checked before any
  * pointer is used.  The queue of edge pixels is a scratch buffer of the
  * context (a word per pixel) with the life and stream rule of rm_bloom's.
- * Out of scope: scene plugins, float targets, banded / sharded / wire renders
+ * Out of scope: float targets, banded / sharded / wire renders
  * and count_evals of the refine (rm_params.count_evals counts the base frame
- * only). */
+ * only).  Scene plugins: rm_refine_ex_rgba8 / rm_render_aa_ex_rgba8 below.
+ *
+ * rm_refine_ex_rgba8 and rm_render_aa_ex_rgba8 take any scene, a scene plugin
+ * included.  For a built-in scene they are rm_refine_rgba8 and
+ * rm_render_aa_rgba8: the same path and the same bytes.  For a plugin the
+ * contract above holds with the plugin's frame in place of the frame: a refined
+ * pixel is, byte for byte, the RGBA8 pack of the tree mean of
+ * rm_render_accumulate's K float frames at u_seed1 = o + 0.5, u_sample_part = 1;
+ * every other pixel keeps its bytes; mask and rm_aa_stats.refined follow the
+ * edge rule on the frame's words.  The uniforms are the context's at the call,
+ * the pass's and the scene's own (rm_set_uniform*).  (rm_refine_rgba8 and
+ * rm_render_aa_rgba8 themselves keep refusing a scene plugin.)
+ *   A plugin's refine kernel is a third code object of the scene (the detect
+ * kernel is compiled in), compiled on the first _ex call after the scene was
+ * loaded and cached by its text, as rm_render_batch_ex's is, so that a scene
+ * never antialiased pays nothing; a call that must compile blocks for that
+ * long.  rm_aa_prepare compiles and loads it now: RM_OK at once for a built-in
+ * scene or when it is loaded already, RM_ERR_NO_SCENE without a scene,
+ * RM_ERR_SCENE for a plugin built with RM_PLUGIN_EVAL_ONLY.
+ * rm_compile_scene_aa is rm_compile_scene for that code object (no GPU needed;
+ * a built-in scene: RM_OK with the compiled-in log; an RM_PLUGIN_EVAL_ONLY
+ * scene: RM_ERR_SCENE).
+ *   A plugin's refine has the lane = (queue entry, sample) layout only: the
+ * environment variable RM_AA_LAYOUT, which selects the other one for the
+ * built-in scenes' measurements, does not apply to a plugin.
+ *   Errors, in the order above: sizes, NULL, samples and threshold; no scene;
+ * then RM_ERR_SCENE for a plugin built with RM_PLUGIN_EVAL_ONLY; mixed
+ * pointers; then RM_ERR_SCENE if the refine kernel fails to compile, its log in
+ * rm_last_error.  In every case the frame is untouched.
+ *   Out of scope: supersampling of a plugin batch, float targets,
+ * RM_AA_LAYOUT=pixel for plugins, count_evals of the refine, banded / sharded /
+ * wire renders. */
 typedef struct rm_aa_params {
     int32_t samples;   /* K: 2, 4 or 8 */
     int32_t threshold; /* 0..255       */
@@ -489,6 +520,12 @@ rm_status rm_refine_rgba8(rm_ctx *ctx, int W, int H, const rm_aa_params *params,
                           rm_aa_stats *stats);
 rm_status rm_render_aa_rgba8(rm_ctx *ctx, int W, int H, const rm_aa_params *params, uint32_t *out, uint8_t *mask,
                              rm_aa_stats *stats);
+rm_status rm_refine_ex_rgba8(rm_ctx *ctx, int W, int H, const rm_aa_params *params, uint32_t *frame, uint8_t *mask,
+                             rm_aa_stats *stats);
+rm_status rm_render_aa_ex_rgba8(rm_ctx *ctx, int W, int H, const rm_aa_params *params, uint32_t *out, uint8_t *mask,
+                                rm_aa_stats *stats);
+rm_status rm_aa_prepare(rm_ctx *ctx);
+rm_status rm_compile_scene_aa(const char *file_name, char *log, size_t log_size);
 
 /* View batches: n poses of the loaded scene rendered by one launch over views x
  * tiles (no counterpart in the reference, whose frame loop draws one pose per

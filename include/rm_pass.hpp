@@ -159,6 +159,9 @@ public:
         return ctx_ && rm_render_batch_ex(ctx_, w, h, views, n, uniforms, nUniforms, out, stats) == RM_OK;
     }
     bool batchPrepare() { return ctx_ && rm_batch_prepare(ctx_) == RM_OK; }
+    // rm.h rm_aa_prepare: compile and load a scene plugin's refine kernel now, not
+    // inside the first RenderTexture::drawAAEx (nothing to do for a built-in scene)
+    bool prepareAA() { return ctx_ && rm_aa_prepare(ctx_) == RM_OK; }
     // rm.h rm_render_batch_aa_rgba8: renderBatch's RGBA8 frames with every view's
     // edge pixels supersampled, view v's frame what setUniform(pose) +
     // RenderTexture::drawAA(shader, samples, threshold) gives.  mask (n * w * h
@@ -308,6 +311,14 @@ public:
         if (!tex_ || fmt_ != RGBA8) return false;
         const rm_aa_params p{samples, threshold};
         return rm_render_aa_rgba8(shader.ctx(), w_, h_, &p, static_cast<uint32_t*>(tex_), nullptr, stats) == RM_OK;
+    }
+    // drawAA for any scene, a scene plugin included (rm_render_aa_ex_rgba8): with
+    // a built-in scene it is drawAA; a plugin's refine kernel is compiled on the
+    // first call after loadFromFile unless Shader::prepareAA did it before.
+    bool drawAAEx(Shader& shader, int samples = 4, int threshold = 32, rm_aa_stats* stats = nullptr) {
+        if (!tex_ || fmt_ != RGBA8) return false;
+        const rm_aa_params p{samples, threshold};
+        return rm_render_aa_ex_rgba8(shader.ctx(), w_, h_, &p, static_cast<uint32_t*>(tex_), nullptr, stats) == RM_OK;
     }
     // RenderTarget::draw(sprite, &post_shader) (main.cpp:210): post.frag over the
     // shader's u_main_tex into this RGBA8 target (rm_post_frag)

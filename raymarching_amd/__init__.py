@@ -10,7 +10,7 @@ multi-GPU frame (``frame.py``).
 from ._lib import EXPORTS, LIB_PATH, POST_SAMPLES, TONEMAPS, RmError, lib  # noqa: F401
 from .api import (Comm, Renderer, RenderTexture, Shader, ShaderLoader, aa_edge_mask, aa_offsets,  # noqa: F401
                   batch_aa_scratch_bytes, post_batch_plan,
-                  comm_get_id, compile_scene, compile_scene_batch, cycle_rows, pack_views, shard_rows, sharded_layout, wire_capacity, render_code_hash, wire_workspace_bytes)
+                  comm_get_id, compile_scene, compile_scene_aa, compile_scene_batch, cycle_rows, pack_views, shard_rows, sharded_layout, wire_capacity, render_code_hash, wire_workspace_bytes)
 from .cameras import cubemap_rays, equirect_rays, fisheye_rays, turntable  # noqa: F401
 from .poses import POSES, S0_POSE  # noqa: F401
 

@@ -40,7 +40,8 @@ EXPORTS = ("rm_create", "rm_destroy", "rm_load_scene", "rm_set_uniform1f", "rm_s
            "rm_batch_aa_scratch_bytes", "rm_refine_batch_rgba8", "rm_render_batch_aa_rgba8",
            "rm_post_batch_plan", "rm_set_post_batch_scratch_limit", "rm_post_frag_batch", "rm_bloom_batch",
            "rm_post_chain_batch",
-           "rm_render_batch_ex", "rm_render_batch_ex_rgba8", "rm_batch_prepare", "rm_compile_scene_batch")
+           "rm_render_batch_ex", "rm_render_batch_ex_rgba8", "rm_batch_prepare", "rm_compile_scene_batch",
+           "rm_refine_ex_rgba8", "rm_render_aa_ex_rgba8", "rm_aa_prepare", "rm_compile_scene_aa")
 
 # include/rm.h RM_ABI_VERSION: the struct layouts below
 ABI_VERSION = 3
@@ -217,6 +218,7 @@ def lib() -> ctypes.CDLL:
                                        c.POINTER(RmStats)], c.c_int),
         "rm_compile_scene": ([cp, vp, c.c_size_t], c.c_int),
         "rm_compile_scene_batch": ([cp, vp, c.c_size_t], c.c_int),
+        "rm_compile_scene_aa": ([cp, vp, c.c_size_t], c.c_int),
         "rm_scene_eval": ([vp, vp, c.c_int64, vp, vp], c.c_int),
         "rm_scene_eval_form": ([vp, vp, c.c_int64, c.c_int, vp, vp, vp], c.c_int),
         "rm_cast_rays": ([vp, vp, c.c_int, vp, c.c_int64, c.c_int, c.POINTER(RmRayHits), c.POINTER(RmStats)], c.c_int),
@@ -225,6 +227,9 @@ def lib() -> ctypes.CDLL:
         "rm_aa_edge_mask": ([c.c_int, c.c_int, c.c_int, vp, vp], c.c_int),
         "rm_refine_rgba8": ([vp, c.c_int, c.c_int, c.POINTER(RmAaParams), vp, vp, c.POINTER(RmAaStats)], c.c_int),
         "rm_render_aa_rgba8": ([vp, c.c_int, c.c_int, c.POINTER(RmAaParams), vp, vp, c.POINTER(RmAaStats)], c.c_int),
+        "rm_refine_ex_rgba8": ([vp, c.c_int, c.c_int, c.POINTER(RmAaParams), vp, vp, c.POINTER(RmAaStats)], c.c_int),
+        "rm_render_aa_ex_rgba8": ([vp, c.c_int, c.c_int, c.POINTER(RmAaParams), vp, vp, c.POINTER(RmAaStats)], c.c_int),
+        "rm_aa_prepare": ([vp], c.c_int),
         "rm_batch_bytes": ([c.c_int, c.c_int, c.c_int, c.c_int, c.POINTER(c.c_int64), c.POINTER(c.c_int64)], c.c_int),
         "rm_render_batch": ([vp, c.c_int, c.c_int, vp, c.c_int, vp, c.POINTER(RmStats)], c.c_int),
         "rm_render_batch_rgba8": ([vp, c.c_int, c.c_int, vp, c.c_int, vp, c.POINTER(RmStats)], c.c_int),

@@ -838,6 +838,32 @@ class Renderer:
         H, W = frame8.shape
         return self._aa(lib().rm_refine_rgba8, W, H, samples, threshold, frame8, mask, stats)
 
+    def render_aa_ex(self, W, H, samples=4, threshold=32, out=None, mask=False, stats=False):
+        """render_aa for any scene, a scene plugin included
+        (rm_render_aa_ex_rgba8).  For a plugin a refined pixel
+        is byte for byte the pack of the tree mean of render_accumulate's
+        `samples` jittered float frames of the plugin, under the renderer's
+        current uniforms, the scene's own included.  A plugin's refine kernel
+        is compiled on the first call after load_scene (aa_prepare compiles it
+        ahead).  For a built-in scene: render_aa.  Arguments and results as
+        render_aa's."""
+        if out is None:
+            out = _torch().empty((H, W), dtype=_torch().int32, device=f"cuda:{self.device}")
+        return self._aa(lib().rm_render_aa_ex_rgba8, W, H, samples, threshold, out, mask, stats)
+
+    def refine_ex(self, frame8, samples=4, threshold=32, mask=False, stats=False):
+        """rm_refine_ex_rgba8: refine for any scene, a scene plugin included;
+        the supersampling step of render_aa_ex on an [H, W] RGBA8 frame, in
+        place."""
+        H, W = frame8.shape
+        return self._aa(lib().rm_refine_ex_rgba8, W, H, samples, threshold, frame8, mask, stats)
+
+    def aa_prepare(self) -> None:
+        """rm_aa_prepare: compile and load the loaded plugin's refine kernel
+        now, not inside the first render_aa_ex / refine_ex (nothing to do for a
+        built-in scene or once it is loaded)."""
+        check(lib().rm_aa_prepare(self._ctx), self._ctx)
+
     # --- adaptive supersampling of a view batch (rm_render_batch_aa_rgba8, rm_refine_batch_rgba8) ---
     def _batch_aa(self, fn, W, H, views, samples, threshold, frames8, mask, refined, stats):
         """frames8: [n, H, W] RGBA8 words, a device tensor or a numpy array
@@ -1095,6 +1121,18 @@ def compile_scene_batch(file_name: str):
     that defines RM_PLUGIN_EVAL_ONLY."""
     buf = ctypes.create_string_buffer(1 << 16)
     st = lib().rm_compile_scene_batch(file_name.encode(), ctypes.cast(buf, ctypes.c_void_p), len(buf))
+    log = buf.value.decode(errors="replace")
+    if st == _lib.STATUS_CODES["RM_ERR_FILE"]:
+        raise _lib.RmError(st, log)
+    return st == 0, log
+
+
+def compile_scene_aa(file_name: str):
+    """rm_compile_scene_aa: compile_scene for the AA form of a plugin's code
+    object (Renderer.render_aa_ex's refine kernel).  (False, log) for a scene
+    that defines RM_PLUGIN_EVAL_ONLY."""
+    buf = ctypes.create_string_buffer(1 << 16)
+    st = lib().rm_compile_scene_aa(file_name.encode(), ctypes.cast(buf, ctypes.c_void_p), len(buf))
     log = buf.value.decode(errors="replace")
     if st == _lib.STATUS_CODES["RM_ERR_FILE"]:
         raise _lib.RmError(st, log)

@@ -14,11 +14,20 @@
 // Nothing waits inside a launch: detect appends to the queue (one atomic add
 // per wave), the stream orders refine after it, and refine reads the count the
 // detect launch left in device memory (the host never does, between the two).
+//
+// A scene plugin's refine kernel (rm_plugin_kernels.h rm_plugin_aa_refine, the
+// AA form of the plugin's translation unit) is compiled by
+// hiprtc from this header's device part: aa_sample, aa_pack, aa_inv and
+// aa_refine_lane_sample.  Under __HIPCC_RTC__ everything else -- the standard
+// headers, the launchers, the detect kernel and the lane = pixel layout -- is
+// left out.
 #pragma once
+#ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
+#endif
 
 #include "rm_aa_rule.h"
 #include "rm_render_direct.h"
@@ -36,6 +45,7 @@ constexpr int kAaHeadWords = 32;
 // measured); RM_AA_LAYOUT=pixel|sample selects one, read at every call so that
 // tools/aa_probe.py can alternate the two in one process.
 enum AaLayout : int { AA_LANE_SAMPLE = 0, AA_LANE_PIXEL = 1 };
+#ifndef __HIPCC_RTC__
 int aa_layout();
 
 // rm_aa_t.hip (the detect kernel is scene-independent integer code)
@@ -47,7 +57,12 @@ hipError_t launch_aa_refine_t(int scene, const FrameConst& F, int samples, int l
 hipError_t launch_aa_refine_o(int scene, const FrameConst& F, int samples, int layout, const uint32_t* count,
                               const uint32_t* queue, uint32_t* frame, hipStream_t s);
 
-#ifdef RM_AA_KERNELS  // the kernels' translation units (the host file takes the launchers above only)
+#endif  // __HIPCC_RTC__
+
+// the kernels' translation units (the host file takes the launchers above only), and a plugin's AA form
+#if defined(RM_AA_KERNELS) || defined(__HIPCC_RTC__)
+
+#ifndef __HIPCC_RTC__
 
 // One wave per 8x8 tile of the frame (tile = blockIdx.x, row-major on a
 // tiles_x-wide grid).  The tile's edge pixels go to the queue in lane order
@@ -71,8 +86,12 @@ __device__ __forceinline__ void aa_detect_tile(const uint32_t* __restrict__ fram
     if (edge) queue[base + (uint32_t)__popcll(b & ((1ull << lane) - 1ull))] = (uint32_t)(y * W + x);
 }
 
+#endif  // __HIPCC_RTC__
+
 // One sample of pixel (x, y): the frame kernels' pixel (render_tile_at,
-// rm_render_direct.h) with the fragment moved by (ox, oy) as
+// rm_render_direct.h; a scene plugin's: plugin_render_tile<false>,
+// rm_plugin_kernels.h, whose timed form of render_pixel is 1, as in
+// rm_shade.h) with the fragment moved by (ox, oy) as
 // rm_render_accumulate moves it -- camera_ray reads the offset from its
 // FrameConst, so it gets a copy with jit_x / jit_y set -- in the timed forms
 // (the exact skips), after post_colour.
@@ -89,7 +108,7 @@ __device__ __forceinline__ V3 aa_sample(const FrameConst& F, int x, int y, float
     Tally cnt;
     V3 c;
     if constexpr (SC == SCENE_T) c = render_pixel<SC, 3, 1, 1>(F, ro, rd, cnt);
-    else c = render_pixel<SC, 3, P::kSettleO ? 1 : 0>(F, ro, rd, cnt);
+    else c = render_pixel<SC, 3, (P::kSettleO || SC == SCENE_PLUGIN) ? 1 : 0>(F, ro, rd, cnt);
     return post_colour<P::kTrim>(c, vig);
 }
 
@@ -153,6 +172,7 @@ __device__ __forceinline__ void aa_refine_lane_sample(const FrameConst& F, int k
     }
 }
 
+#ifndef __HIPCC_RTC__
 // AA_LANE_PIXEL: the samples of a pixel one after the other on its lane; the
 // tree as a binary counter over three partial sums (sample k closes the
 // subtrees its low one bits name).
@@ -239,6 +259,8 @@ hipError_t launch_aa_refine_scene(const FrameConst& F, int samples, int layout, 
     return launch_aa_refine_as<SC, AA_LANE_SAMPLE>(F, samples, count, queue, frame, s);
 }
 
-#endif  // RM_AA_KERNELS
+#endif  // __HIPCC_RTC__
+
+#endif  // RM_AA_KERNELS || __HIPCC_RTC__
 
 }  // namespace rm

@@ -1,6 +1,9 @@
-// rm_aa_host.cpp -- rm_refine_rgba8 and rm_render_aa_rgba8 (include/rm.h):
+// rm_aa_host.cpp -- rm_refine_rgba8, rm_render_aa_rgba8, their _ex forms that
+// take any scene and rm_aa_prepare (include/rm.h):
 // their argument checks, the context's queue, the staging of host buffers and
-// the launch sequence (kernels: rm_aa.h, rm_aa_t.hip, rm_aa_o.hip).
+// the launch sequence (kernels: rm_aa.h, rm_aa_t.hip, rm_aa_o.hip; a scene
+// plugin's refine: the AA form of its translation unit, rm_plugin_host.cpp
+// aa_ready).
 #include <cstring>
 
 #include "rm_aa.h"
@@ -49,8 +52,11 @@ rm_status refine_dev(rm_ctx *ctx, int W, int H, const rm_aa_params &p, uint32_t 
     ctx->aa_pending = true;
     mark_done(ctx);
     if (stats) RM_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-    const int layout = rm::aa_layout();
-    e = ctx->scene == rm::SCENE_S0 || ctx->scene == rm::SCENE_T
+    const int layout = rm::aa_layout();  // (a plugin has the lane = (entry, sample) layout alone)
+    e = ctx->scene == rm::SCENE_PLUGIN
+            ? rmplugin::launch_aa_refine(ctx->plugin, F, ctx->uniform_values, rmaa::samples_shift(p.samples), count,
+                                         queue, frame, ctx->stream)
+        : ctx->scene == rm::SCENE_S0 || ctx->scene == rm::SCENE_T
             ? rm::launch_aa_refine_t(ctx->scene, F, p.samples, layout, count, queue, frame, ctx->stream)
             : rm::launch_aa_refine_o(ctx->scene, F, p.samples, layout, count, queue, frame, ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "supersampling refine launch");
@@ -66,26 +72,46 @@ rm_status refine_dev(rm_ctx *ctx, int W, int H, const rm_aa_params &p, uint32_t 
     return RM_OK;
 }
 
-// the checks of both calls, before any pointer is used
-rm_status aa_check(rm_ctx *ctx, const char *what, int W, int H, const rm_aa_params *p, const uint32_t *frame) {
+// what the _ex calls and rm_aa_prepare ask of a loaded plugin: it must have render kernels
+rm_status aa_plugin_scene(rm_ctx *ctx) {
+    if (!ctx->plugin.render)
+        return fail(ctx, RM_ERR_SCENE, "scene plugin was compiled with RM_PLUGIN_EVAL_ONLY (no render kernel)");
+    return RM_OK;
+}
+
+// the loaded plugin's refine kernel, compiled and loaded if it is not yet
+rm_status aa_plugin_ready(rm_ctx *ctx) {
+    std::string err;
+    hipError_t e = hipSuccess;
+    if (rmplugin::aa_ready(ctx->plugin, err, e)) return RM_OK;
+    if (e != hipSuccess) return hip_fail(ctx, e, "scene plugin AA module load");
+    return fail(ctx, RM_ERR_SCENE, "scene plugin \"" + ctx->plugin.file + "\": the AA form failed to compile:\n" + err);
+}
+
+// the checks of the calls, before any pointer is used; any_scene: the _ex calls, which take a scene plugin
+rm_status aa_check(rm_ctx *ctx, const char *what, int W, int H, const rm_aa_params *p, const uint32_t *frame,
+                   bool any_scene) {
     if (W <= 0 || H <= 0 || (int64_t)W * H >= rmaa::kMaxPixels || !p || !frame)
         return fail(ctx, RM_ERR_INVALID_ARGUMENT, std::string(what) + ": bad arguments");
     if (!rmaa::samples_ok(p->samples) || !rmaa::threshold_ok(p->threshold))
         return fail(ctx, RM_ERR_INVALID_ARGUMENT, std::string(what) + ": samples must be 2, 4 or 8 and threshold 0..255");
     if (ctx->scene < 0) return fail(ctx, RM_ERR_NO_SCENE, "no scene loaded (rm_load_scene)");
-    if (ctx->scene == rm::SCENE_PLUGIN) return fail(ctx, RM_ERR_SCENE, "adaptive supersampling: built-in scenes only");
+    if (ctx->scene == rm::SCENE_PLUGIN)
+        return any_scene ? aa_plugin_scene(ctx) : fail(ctx, RM_ERR_SCENE, "adaptive supersampling: built-in scenes only");
     return RM_OK;
 }
 
 // render: rm_render_rgba8 into the frame first (rm_render_aa_rgba8)
 rm_status aa_run(rm_ctx *ctx, const char *what, int W, int H, const rm_aa_params *p, uint32_t *frame, uint8_t *mask,
-                 rm_aa_stats *stats, bool render) {
+                 rm_aa_stats *stats, bool render, bool any_scene) {
     if (!ctx) return RM_ERR_INVALID_ARGUMENT;
-    if (rm_status st = aa_check(ctx, what, W, H, p, frame)) return st;
+    if (rm_status st = aa_check(ctx, what, W, H, p, frame, any_scene)) return st;
     RM_HIP(hipSetDevice(ctx->device));
     const bool dev = is_device_ptr(frame);
     if (mask && is_device_ptr(mask) != dev)
         return fail(ctx, RM_ERR_INVALID_ARGUMENT, std::string(what) + ": host and device pointers mixed");
+    if (ctx->scene == rm::SCENE_PLUGIN)  // (before anything is written: a form that fails to compile leaves the frame)
+        if (rm_status st = aa_plugin_ready(ctx)) return st;
     if (stats) std::memset(stats, 0, sizeof(*stats));
     const size_t px = (size_t)W * H, frame_bytes = px * sizeof(uint32_t);
     char *tmp = nullptr;
@@ -122,12 +148,31 @@ extern "C" {
 
 rm_status rm_refine_rgba8(rm_ctx *ctx, int W, int H, const rm_aa_params *params, uint32_t *frame, uint8_t *mask,
                           rm_aa_stats *stats) {
-    return aa_run(ctx, "rm_refine_rgba8", W, H, params, frame, mask, stats, false);
+    return aa_run(ctx, "rm_refine_rgba8", W, H, params, frame, mask, stats, false, false);
 }
 
 rm_status rm_render_aa_rgba8(rm_ctx *ctx, int W, int H, const rm_aa_params *params, uint32_t *out, uint8_t *mask,
                              rm_aa_stats *stats) {
-    return aa_run(ctx, "rm_render_aa_rgba8", W, H, params, out, mask, stats, true);
+    return aa_run(ctx, "rm_render_aa_rgba8", W, H, params, out, mask, stats, true, false);
+}
+
+rm_status rm_refine_ex_rgba8(rm_ctx *ctx, int W, int H, const rm_aa_params *params, uint32_t *frame, uint8_t *mask,
+                             rm_aa_stats *stats) {
+    return aa_run(ctx, "rm_refine_ex_rgba8", W, H, params, frame, mask, stats, false, true);
+}
+
+rm_status rm_render_aa_ex_rgba8(rm_ctx *ctx, int W, int H, const rm_aa_params *params, uint32_t *out, uint8_t *mask,
+                                rm_aa_stats *stats) {
+    return aa_run(ctx, "rm_render_aa_ex_rgba8", W, H, params, out, mask, stats, true, true);
+}
+
+rm_status rm_aa_prepare(rm_ctx *ctx) {
+    if (!ctx) return RM_ERR_INVALID_ARGUMENT;
+    if (ctx->scene < 0) return fail(ctx, RM_ERR_NO_SCENE, "no scene loaded (rm_load_scene)");
+    if (ctx->scene != rm::SCENE_PLUGIN) return RM_OK;  // (compiled in)
+    if (rm_status st = aa_plugin_scene(ctx)) return st;
+    RM_HIP(hipSetDevice(ctx->device));
+    return aa_plugin_ready(ctx);
 }
 
 }  // extern "C"

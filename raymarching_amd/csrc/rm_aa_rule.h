@@ -18,9 +18,14 @@
 // Every offset o and o + 0.5 is exact in f32, so u_seed1 = o + 0.5 makes
 // rm_render_accumulate render exactly that sample.
 #pragma once
+#ifdef __HIPCC_RTC__  // compiled by hiprtc (a scene plugin's AA form, rm_plugin_kernels.h)
+using __hip_internal::int64_t;
+using __hip_internal::uint32_t;
+#else
 #include <cstdint>
+#endif
 
-#if defined(__HIPCC__)
+#if defined(__HIPCC__) || defined(__HIPCC_RTC__)
 #define RM_AA_HD __host__ __device__
 #else
 #define RM_AA_HD

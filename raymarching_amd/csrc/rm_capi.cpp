@@ -807,8 +807,8 @@ rm_status rm_scene_eval_form(rm_ctx *ctx, const float *points, int64_t n, int fo
     return scene_eval_form(ctx, points, n, form, dist, material, aux, "rm_scene_eval_form");
 }
 
-// rm_compile_scene; batch: the batch form of the code object (rm_compile_scene_batch)
-static rm_status compile_scene(const char *file_name, char *log, size_t log_size, bool batch) {
+// rm_compile_scene; form: the batch or the AA form of the code object (rm_compile_scene_batch, rm_compile_scene_aa)
+static rm_status compile_scene(const char *file_name, char *log, size_t log_size, rmplugin::Form form) {
     if (!file_name) return RM_ERR_INVALID_ARGUMENT;
     std::string src, err, clog;
     int sc = -1;
@@ -820,7 +820,7 @@ static rm_status compile_scene(const char *file_name, char *log, size_t log_size
     } else {
         rmplugin::Code code;
         rmuniform::Table uniforms;
-        if (!rmplugin::compile(src, file_name, code, clog, uniforms, batch)) st = RM_ERR_SCENE;
+        if (!rmplugin::compile(src, file_name, code, clog, uniforms, form)) st = RM_ERR_SCENE;
     }
     if (log && log_size > 0) {
         size_t k = clog.size() < log_size - 1 ? clog.size() : log_size - 1;
@@ -831,11 +831,15 @@ static rm_status compile_scene(const char *file_name, char *log, size_t log_size
 }
 
 rm_status rm_compile_scene(const char *file_name, char *log, size_t log_size) {
-    return compile_scene(file_name, log, log_size, false);
+    return compile_scene(file_name, log, log_size, rmplugin::FORM_FRAME);
 }
 
 rm_status rm_compile_scene_batch(const char *file_name, char *log, size_t log_size) {
-    return compile_scene(file_name, log, log_size, true);
+    return compile_scene(file_name, log, log_size, rmplugin::FORM_BATCH);
+}
+
+rm_status rm_compile_scene_aa(const char *file_name, char *log, size_t log_size) {
+    return compile_scene(file_name, log, log_size, rmplugin::FORM_AA);
 }
 
 int rm_abi_version(void) { return RM_ABI_VERSION; }

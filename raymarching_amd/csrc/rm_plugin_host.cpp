@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <vector>
 
+#include <algorithm>
 #include <cctype>
 #include <cstdlib>
 #include <fstream>
@@ -187,7 +188,7 @@ std::mutex g_mu;
 std::map<std::string, Code> g_cache;
 
 std::string translation_unit(const std::string& src, const std::string& file, const rmuniform::Table& uniforms,
-                             bool batch) {
+                             Form form) {
     std::string name;
     for (char c : file) {
         if (c == '"' || c == '\\') name += '\\';
@@ -219,7 +220,9 @@ std::string translation_unit(const std::string& src, const std::string& file, co
     }
     // the batch form is the frame form's text behind one #define: the same scene text in the same two instances
     // under the same pragmas, so that a view's bytes are the frame kernels' (rm_plugin.h, rm_plugin_kernels.h)
-    if (batch) head = "#define RM_PLUGIN_BATCH 1\n" + head;
+    if (form == FORM_BATCH) head = "#define RM_PLUGIN_BATCH 1\n" + head;
+    // (the AA form likewise, so that a refined sample rounds as the frame kernel's pixel does)
+    if (form == FORM_AA) head = "#define RM_PLUGIN_AA 1\n" + head;
     return head + "#include \"rm_plugin.h\"\n" + defines +
            instance("namespace rm {\nnamespace glsl {\n", "}  // namespace glsl\n}  // namespace rm\n", "", "") +
            instance("namespace rm {\nnamespace glsl {\nnamespace probe {\n",
@@ -231,16 +234,16 @@ std::string translation_unit(const std::string& src, const std::string& file, co
 }  // namespace
 
 bool compile(const std::string& src, const std::string& file, Code& code, std::string& log,
-             rmuniform::Table& uniforms, bool batch) {
+             rmuniform::Table& uniforms, Form form) {
     std::string scene;
     if (!rmuniform::parse(src, file, uniforms, scene, log)) return false;
-    const std::string tu = translation_unit(scene, file, uniforms, batch);
+    const std::string tu = translation_unit(scene, file, uniforms, form);
     log.clear();
-    // debugging: the TU and its code object (a cached one too), the batch form's beside the frame form's
+    // debugging: the TU and its code object (a cached one too), the batch and AA forms' beside the frame form's
     auto dump = [&](const Code& c) {
         const char* dir = std::getenv("RM_PLUGIN_DUMP");
         if (!dir) return;
-        const std::string stem = std::string(dir) + (batch ? "/plugin_batch" : "/plugin");
+        const std::string stem = std::string(dir) + (form == FORM_BATCH ? "/plugin_batch" : form == FORM_AA ? "/plugin_aa" : "/plugin");
         std::ofstream(stem + "_tu.hip") << tu;
         std::ofstream(stem + ".co", std::ios::binary).write(c->data(), (std::streamsize)c->size());
     };
@@ -315,12 +318,13 @@ hipError_t load(const Code& code, int uniform_slots, Module& m) {
     }
     n.code = code;
     n.uniform_slots = uniform_slots;
-    unload(m);  // (the batch form of the scene before with it)
+    unload(m);  // (the batch and AA forms of the scene before with it)
     m = n;
     return hipSuccess;
 }
 
 void unload(Module& m) {
+    if (m.aa_mod) (void)hipModuleUnload(m.aa_mod);
     if (m.batch_mod) (void)hipModuleUnload(m.batch_mod);
     if (m.mod) (void)hipModuleUnload(m.mod);
     m = Module();
@@ -331,7 +335,7 @@ bool batch_ready(Module& m, std::string& err, hipError_t& e) {
     if (m.render_batch) return true;
     Code code;
     rmuniform::Table uniforms;
-    if (!compile(m.src, m.file, code, err, uniforms, true)) return false;
+    if (!compile(m.src, m.file, code, err, uniforms, FORM_BATCH)) return false;
     hipModule_t mod = nullptr;
     e = hipModuleLoadData(&mod, code->data());
     if (e == hipSuccess) {
@@ -347,6 +351,48 @@ bool batch_ready(Module& m, std::string& err, hipError_t& e) {
     }
     m.batch_mod = mod;
     return true;
+}
+
+bool aa_ready(Module& m, std::string& err, hipError_t& e) {
+    e = hipSuccess;
+    if (m.aa_refine) return true;
+    Code code;
+    rmuniform::Table uniforms;
+    if (!compile(m.src, m.file, code, err, uniforms, FORM_AA)) return false;
+    hipModule_t mod = nullptr;
+    hipFunction_t fn = nullptr;
+    int dev = 0, cus = 0, per_cu = 0;
+    e = hipModuleLoadData(&mod, code->data());
+    if (e == hipSuccess) {
+        e = hipModuleGetFunction(&fn, mod, "rm_plugin_aa_refine");
+        // the grid, as rm_aa.h's launch_aa_refine_as fixes it: the one-wave workgroups the device holds at once
+        if (e == hipSuccess) e = hipGetDevice(&dev);
+        if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        if (e == hipSuccess) e = hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, 0);
+        if (e != hipSuccess) (void)hipModuleUnload(mod);
+    }
+    if (e != hipSuccess) {
+        err = std::string("scene plugin AA module load: ") + hipGetErrorString(e);
+        return false;
+    }
+    m.aa_mod = mod;
+    m.aa_refine = fn;
+    m.aa_grid = (unsigned)std::max(1, cus * std::max(per_cu, 1));
+    return true;
+}
+
+hipError_t launch_aa_refine(const Module& m, const rm::FrameConst& F, const uint32_t* uniforms, int kshift,
+                            const uint32_t* count, const uint32_t* queue, uint32_t* frame, hipStream_t s) {
+    if (!m.aa_refine) return hipErrorInvalidDeviceFunction;
+    rm::FrameConst f = F;
+    int k = kshift;
+    const uint32_t *c = count, *q = queue;
+    uint32_t* o = frame;
+    // (the uniform block is read now, as launch_render's)
+    void* with_block[] = {&f, const_cast<uint32_t*>(uniforms), &k, &c, &q, &o};
+    void* args[] = {&f, &k, &c, &q, &o};
+    return hipModuleLaunchKernel(m.aa_refine, m.aa_grid, 1, 1, 64, 1, 1, 0, s, m.uniform_slots > 0 ? with_block : args,
+                                 nullptr);
 }
 
 hipError_t launch_render_batch(const Module& m, const void* records, int W, int H, int n, void* out, bool rgba8,

@@ -31,11 +31,15 @@ std::string glsl_source(const std::string& src);
 // compiler sees the source with the declarations blanked, so two sources that
 // differ in a default value share a code object and nothing else.  On failure
 // `log` holds the diagnostics.
-// `batch`: the batch form of the translation unit (rm_plugin.h RM_PLUGIN_BATCH):
-// the same scene text and options, one kernel, rm_plugin_render_batch; a scene
-// that defines RM_PLUGIN_EVAL_ONLY has no such form and fails to compile.
+// `form`: the frame form, or one of the one-kernel forms of the translation
+// unit, the frame form's text behind one #define at its head -- the same scene
+// text and options: FORM_BATCH (rm_plugin.h RM_PLUGIN_BATCH), whose kernel is
+// rm_plugin_render_batch, and FORM_AA (RM_PLUGIN_AA), whose kernel is
+// rm_plugin_aa_refine.  A scene that defines RM_PLUGIN_EVAL_ONLY has neither and
+// fails to compile.
+enum Form : int { FORM_FRAME = 0, FORM_BATCH = 1, FORM_AA = 2 };
 bool compile(const std::string& src, const std::string& file, Code& code, std::string& log,
-             rmuniform::Table& uniforms, bool batch = false);
+             rmuniform::Table& uniforms, Form form = FORM_FRAME);
 
 struct Module {
     hipModule_t mod = nullptr;
@@ -52,6 +56,11 @@ struct Module {
     std::string src, file;  // the preprocessed scene source rm_load_scene compiled, and its file name
     hipModule_t batch_mod = nullptr;
     hipFunction_t render_batch = nullptr;
+    // the AA form (rm_refine_ex_rgba8): as the batch form, by aa_ready; the refine's grid, as many one-wave
+    // workgroups as the device holds at once, is fixed when the form is loaded
+    hipModule_t aa_mod = nullptr;
+    hipFunction_t aa_refine = nullptr;
+    unsigned aa_grid = 0;
 };
 // on the current device; m keeps its old module on failure
 hipError_t load(const Code& code, int uniform_slots, Module& m);
@@ -59,6 +68,13 @@ void unload(Module& m);
 // The batch form of m's scene, compiled (cached by text, as compile caches) and loaded on the current device; at
 // once if it is loaded already.  False with `err` set: `e` is hipSuccess if the compilation failed.
 bool batch_ready(Module& m, std::string& err, hipError_t& e);
+// The AA form likewise (rm_plugin_aa_refine and its grid).
+bool aa_ready(Module& m, std::string& err, hipError_t& e);
+// rm_aa.h's refine launch for m's scene: the queue of `*count` pixel indices at `queue` (device memory, the
+// compiled-in detect kernel's), K = 1 << kshift samples per pixel into `frame`; `uniforms` as launch_render's;
+// hipErrorInvalidDeviceFunction before aa_ready
+hipError_t launch_aa_refine(const Module& m, const rm::FrameConst& F, const uint32_t* uniforms, int kshift,
+                            const uint32_t* count, const uint32_t* queue, uint32_t* frame, hipStream_t s);
 // bytes of one view's record: the FrameConst, then the uniform block at rm_plugin.h's kUniformOffset
 constexpr size_t kBatchUniformOffset = (sizeof(rm::FrameConst) + 15) & ~(size_t)15;
 static_assert(kBatchUniformOffset == 592, "include/rm.h states a plugin record's bytes");

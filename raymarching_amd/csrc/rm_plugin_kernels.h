@@ -8,6 +8,9 @@
 #pragma once
 #include "rm_rays.h"
 #include "rm_shade.h"
+#ifdef RM_PLUGIN_AA
+#include "rm_aa.h"
+#endif
 
 #ifdef RM_UNIFORM_SLOTS
 #define RM_UNIFORM_PARAM rm::glsl::UniformBlock,
@@ -92,6 +95,18 @@ extern "C" __global__ __launch_bounds__(64) void rm_plugin_render_batch(const vo
     const size_t frame = (size_t)G.W * (size_t)G.H * (rgba8 ? sizeof(uint32_t) : sizeof(float4));
     rm::plugin_render_tile<false>(G, static_cast<char*>(out) + (size_t)blockIdx.z * frame, rgba8, nullptr);
 }
+#elif defined(RM_PLUGIN_AA)
+// The AA form of the translation unit (include/rm.h rm_refine_ex_rgba8) has this kernel alone:
+// rm_aa.h's refine in the lane = (queue entry, sample) layout -- one-wave workgroups striding over the queue of
+// edge pixels the compiled-in detect kernel left, each sample the timed kernel's pixel (aa_sample calls what
+// plugin_render_tile<false> calls) with the fragment moved by the lane's offset.  F and the uniform block are the
+// first two parameters, where the scene's functions read them (rm_plugin.h).
+extern "C" __global__ __launch_bounds__(64) void rm_plugin_aa_refine(rm::FrameConst F, RM_UNIFORM_PARAM int kshift,
+                                                                     const uint32_t* count, const uint32_t* queue,
+                                                                     uint32_t* frame) {
+    RM_UNIFORM_PRELOAD();
+    rm::aa_refine_lane_sample<rm::SCENE_PLUGIN>(F, kshift, count, queue, frame);
+}
 #else
 extern "C" __global__ __launch_bounds__(64) void rm_plugin_render(rm::FrameConst F, RM_UNIFORM_PARAM void* out,
                                                                   int rgba8, unsigned long long* evals) {
@@ -111,12 +126,14 @@ extern "C" __global__ __launch_bounds__(64) void rm_plugin_shade(rm::FrameConst 
     RM_UNIFORM_PRELOAD();
     rm::shade_rays_one<rm::SCENE_PLUGIN, rm::SHADE_PER_LAUNCH, rm::SHADE_PER_LAUNCH>(F, Q);
 }
-#endif  // RM_PLUGIN_BATCH
+#endif  // RM_PLUGIN_BATCH, RM_PLUGIN_AA
 #elif defined(RM_PLUGIN_BATCH)
 #error "the scene defines RM_PLUGIN_EVAL_ONLY (no render kernel): it has no batch form"
+#elif defined(RM_PLUGIN_AA)
+#error "the scene defines RM_PLUGIN_EVAL_ONLY (no render kernel): it has no AA form"
 #endif
 
-#ifndef RM_PLUGIN_BATCH
+#if !defined(RM_PLUGIN_BATCH) && !defined(RM_PLUGIN_AA)
 // sceneSDF(p) at explicit points (rm_scene_eval)
 extern "C" __global__ __launch_bounds__(256) void rm_plugin_eval(rm::FrameConst F, RM_UNIFORM_PARAM const float* pts,
                                                                  long long n, float* dist, float* mat) {
@@ -144,4 +161,4 @@ extern "C" __global__ __launch_bounds__(256) void rm_plugin_cast(rm::FrameConst 
     RM_UNIFORM_PRELOAD();
     rm::cast_rays_one<rm::SCENE_PLUGIN>(F, Q, inside);
 }
-#endif  // RM_PLUGIN_BATCH
+#endif  // RM_PLUGIN_BATCH, RM_PLUGIN_AA
