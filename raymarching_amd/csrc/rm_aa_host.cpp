@@ -1,13 +1,14 @@
 // rm_aa_host.cpp -- rm_refine_rgba8, rm_render_aa_rgba8, their _ex forms that
 // take any scene and rm_aa_prepare (include/rm.h):
-// their argument checks, the context's queue, the staging of host buffers and
-// the launch sequence (kernels: rm_aa.h, rm_aa_t.hip, rm_aa_o.hip; a scene
-// plugin's refine: the AA form of its translation unit, rm_plugin_host.cpp
-// aa_ready).
+// their argument checks, the context's queue, the staging of host buffers
+// (rm_stage.h) and the launch sequence (kernels: rm_aa.h, rm_aa_t.hip,
+// rm_aa_o.hip; a scene plugin's refine: the AA form of its translation unit,
+// rm_plugin_host.cpp aa_ready).
 #include <cstring>
 
 #include "rm_aa.h"
 #include "rm_ctx.h"
+#include "rm_stage.h"
 #include "rm_trace.h"
 
 using rm::FrameConst;
@@ -16,29 +17,13 @@ using namespace rmhost;
 
 namespace {
 
-// The queue for a W x H frame on the context's stream.  One buffer per context
-// (bloom's rule, rm_post_batch_host.cpp bloom_scratch): a refine on another stream than
-// the last one first waits, on the device, for that one, marked when the
-// context left its stream (rm_ctx_streams.cpp set_stream).
-rm_status aa_scratch(rm_ctx *ctx, int W, int H) {
-    if (ctx->aa_ev && ctx->aa_stream != ctx->stream) RM_HIP(hipStreamWaitEvent(ctx->stream, ctx->aa_ev, 0));
-    const size_t words = (size_t)rm::kAaHeadWords + (size_t)W * H;
-    if (words > ctx->aa_words) {
-        if (ctx->aa_queue) RM_HIP(hipFree(ctx->aa_queue));  // (waits for the launches that use it)
-        ctx->aa_queue = nullptr;
-        ctx->aa_words = 0;
-        RM_HIP(hipMalloc(&ctx->aa_queue, words * sizeof(uint32_t)));
-        ctx->aa_words = words;
-    }
-    return RM_OK;
-}
-
 // detect, then refine, on the context's stream; device pointers
 rm_status refine_dev(rm_ctx *ctx, int W, int H, const rm_aa_params &p, uint32_t *frame, uint8_t *mask,
                      rm_aa_stats *stats) {
     rm::TraceRange range("rm_refine");
-    if (rm_status st = aa_scratch(ctx, W, H)) return st;
-    uint32_t *count = ctx->aa_queue, *queue = ctx->aa_queue + rm::kAaHeadWords;
+    rm_ctx::Scratch &sc = ctx->scratch[rm_ctx::kScratchAa];  // the queue for a W x H frame
+    if (rm_status st = scratch_acquire(ctx, sc, ((size_t)rm::kAaHeadWords + (size_t)W * H) * sizeof(uint32_t))) return st;
+    uint32_t *count = sc.as<uint32_t>(), *queue = count + rm::kAaHeadWords;
     RowPart part;
     (void)rm::band_part(H, 1, 0, part);  // the whole frame, as rm_render_rgba8's launch
     FrameConst F = frame_const(ctx, W, H, part, H);
@@ -48,8 +33,7 @@ rm_status refine_dev(rm_ctx *ctx, int W, int H, const rm_aa_params &p, uint32_t 
     if (stats) RM_HIP(hipEventRecord(ctx->ev0, ctx->stream));
     hipError_t e = rm::launch_aa_detect(frame, W, H, p.threshold, mask, count, queue, ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "supersampling detect launch");
-    ctx->aa_stream = ctx->stream;
-    ctx->aa_pending = true;
+    scratch_used(ctx, sc);
     mark_done(ctx);
     if (stats) RM_HIP(hipEventRecord(ctx->ev1, ctx->stream));
     const int layout = rm::aa_layout();  // (a plugin has the lane = (entry, sample) layout alone)
@@ -60,16 +44,7 @@ rm_status refine_dev(rm_ctx *ctx, int W, int H, const rm_aa_params &p, uint32_t 
             ? rm::launch_aa_refine_t(ctx->scene, F, p.samples, layout, count, queue, frame, ctx->stream)
             : rm::launch_aa_refine_o(ctx->scene, F, p.samples, layout, count, queue, frame, ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "supersampling refine launch");
-    if (stats) {
-        RM_HIP(hipEventRecord(ctx->aa_ev2, ctx->stream));
-        RM_HIP(hipEventSynchronize(ctx->aa_ev2));
-        uint32_t n = 0;
-        RM_HIP(hipMemcpy(&n, count, sizeof(n), hipMemcpyDeviceToHost));
-        stats->refined = (int64_t)n;
-        RM_HIP(hipEventElapsedTime(&stats->detect_ms, ctx->ev0, ctx->ev1));
-        RM_HIP(hipEventElapsedTime(&stats->refine_ms, ctx->ev1, ctx->aa_ev2));
-    }
-    return RM_OK;
+    return stats ? refine_stats(ctx, count, stats) : RM_OK;
 }
 
 // what the _ex calls and rm_aa_prepare ask of a loaded plugin: it must have render kernels
@@ -114,35 +89,39 @@ rm_status aa_run(rm_ctx *ctx, const char *what, int W, int H, const rm_aa_params
         if (rm_status st = aa_plugin_ready(ctx)) return st;
     if (stats) std::memset(stats, 0, sizeof(*stats));
     const size_t px = (size_t)W * H, frame_bytes = px * sizeof(uint32_t);
-    char *tmp = nullptr;
-    if (!dev) RM_HIP(hipMalloc(&tmp, frame_bytes + (mask ? px : 0)));  // host buffers: staged
-    uint32_t *frame_d = dev ? frame : reinterpret_cast<uint32_t *>(tmp);
-    uint8_t *mask_d = dev || !mask ? mask : reinterpret_cast<uint8_t *>(tmp + frame_bytes);
-    rm_status st = RM_OK;
-    hipError_t e = hipSuccess;
-    if (render) {
+    Stage stage;  // host buffers: staged
+    if (!dev) {
+        stage.add(frame, frame_bytes, !render, true);
+        stage.add(mask, px, false, true);
+    }
+    rm_status st = stage.begin(ctx, "supersampling: staging");
+    uint32_t *frame_d = dev ? frame : stage.dev<uint32_t>(0);
+    uint8_t *mask_d = dev ? mask : stage.dev<uint8_t>(1);
+    if (st == RM_OK && render) {
         rm_stats base;
         st = render_any(ctx, W, H, H, 1, 0, 0, -1, frame_d, true, stats ? &base : nullptr);
         if (st == RM_OK && stats) stats->base_ms = base.kernel_ms;
-    } else if (!dev) {
-        e = hipMemcpyAsync(frame_d, frame, frame_bytes, hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) st = hip_fail(ctx, e, "supersampling: staging");
     }
     if (st == RM_OK) st = refine_dev(ctx, W, H, *p, frame_d, mask_d, stats);
-    if (!dev) {
-        if (st == RM_OK) {
-            e = hipMemcpyAsync(frame, frame_d, frame_bytes, hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess && mask) e = hipMemcpyAsync(mask, mask_d, px, hipMemcpyDeviceToHost, ctx->stream);
-            if (e != hipSuccess) st = hip_fail(ctx, e, "supersampling: staging");
-        }
-        e = hipStreamSynchronize(ctx->stream);  // (also after a failure: tmp may be in use)
-        if (st == RM_OK && e != hipSuccess) st = hip_fail(ctx, e, what);
-        (void)hipFree(tmp);
-    }
-    return st;
+    return stage.end(ctx, st, what);
 }
 
 }  // namespace
+
+namespace rmhost {
+
+rm_status refine_stats(rm_ctx *ctx, const uint32_t *count, rm_aa_stats *stats) {
+    RM_HIP(hipEventRecord(ctx->aa_ev2, ctx->stream));
+    RM_HIP(hipEventSynchronize(ctx->aa_ev2));
+    uint32_t n = 0;
+    RM_HIP(hipMemcpy(&n, count, sizeof(n), hipMemcpyDeviceToHost));
+    stats->refined = (int64_t)n;
+    RM_HIP(hipEventElapsedTime(&stats->detect_ms, ctx->ev0, ctx->ev1));
+    RM_HIP(hipEventElapsedTime(&stats->refine_ms, ctx->ev1, ctx->aa_ev2));
+    return RM_OK;
+}
+
+}  // namespace rmhost
 
 extern "C" {
 

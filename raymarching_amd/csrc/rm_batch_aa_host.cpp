@@ -8,6 +8,7 @@
 
 #include "rm_batch_aa.h"
 #include "rm_ctx.h"
+#include "rm_stage.h"
 #include "rm_trace.h"
 
 using rm::FrameConst;
@@ -18,38 +19,22 @@ namespace {
 // include/rm.h's size rule of the three calls
 bool size_ok(int W, int H, int n) { return rm::batch_size_ok(W, H, n) && (int64_t)W * H < rmaa::kMaxPixels; }
 
-// The scratch for n views of W x H on the context's stream.  One buffer per
-// context (bloom's rule, as rm_aa_host.cpp aa_scratch): a call on another
-// stream than the last one first waits, on the device, for that one, marked
-// when the context left its stream (rm_ctx_streams.cpp set_stream).
-rm_status batch_aa_scratch(rm_ctx *ctx, const rmbaa::Layout &l) {
-    if (ctx->baa_ev && ctx->baa_stream != ctx->stream) RM_HIP(hipStreamWaitEvent(ctx->stream, ctx->baa_ev, 0));
-    if (l.words > ctx->baa_words) {
-        if (ctx->baa_scratch) RM_HIP(hipFree(ctx->baa_scratch));  // (waits for the launches that use it)
-        ctx->baa_scratch = nullptr;
-        ctx->baa_words = 0;
-        RM_HIP(hipMalloc(&ctx->baa_scratch, (size_t)l.words * sizeof(uint32_t)));
-        ctx->baa_words = (size_t)l.words;
-    }
-    return RM_OK;
-}
-
 // count memset, detect, plan, refine, on the context's stream; device pointers
 rm_status refine_batch_dev(rm_ctx *ctx, const FrameConst &F, const void *rec_d, int n, const rm_aa_params &p,
                            uint32_t *frames, uint8_t *mask, uint32_t *refined, rm_aa_stats *stats) {
     rm::TraceRange range("rm_refine_batch");
     const rmbaa::Layout l = rmbaa::layout(F.W, F.H, n);
-    if (rm_status st = batch_aa_scratch(ctx, l)) return st;
-    uint32_t *counters = ctx->baa_scratch + l.counters, *prefix = ctx->baa_scratch + l.plan,
-             *queue = ctx->baa_scratch + l.queue;
+    rm_ctx::Scratch &sc = ctx->scratch[rm_ctx::kScratchBatchAa];  // the scratch for n views of W x H
+    if (rm_status st = scratch_acquire(ctx, sc, (size_t)l.words * sizeof(uint32_t))) return st;
+    uint32_t *counters = sc.as<uint32_t>() + l.counters, *prefix = sc.as<uint32_t>() + l.plan,
+             *queue = sc.as<uint32_t>() + l.queue;
     const uint32_t cstride = rm::batch_aa_counter_stride();
     if (stats && !ctx->aa_ev2) RM_HIP(hipEventCreate(&ctx->aa_ev2));
     RM_HIP(hipMemsetAsync(counters, 0, (size_t)n * cstride * sizeof(uint32_t), ctx->stream));
     if (stats) RM_HIP(hipEventRecord(ctx->ev0, ctx->stream));
     hipError_t e = rm::launch_batch_aa_detect(frames, F.W, F.H, n, p.threshold, mask, counters, cstride, queue, ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "batch supersampling detect launch");
-    ctx->baa_stream = ctx->stream;
-    ctx->baa_pending = true;
+    scratch_used(ctx, sc);
     mark_done(ctx);
     e = rm::launch_batch_aa_plan(counters, cstride, n, p.samples, prefix, refined, ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "batch supersampling plan launch");
@@ -60,16 +45,8 @@ rm_status refine_batch_dev(rm_ctx *ctx, const FrameConst &F, const void *rec_d, 
             : rm::launch_batch_aa_refine_o(ctx->scene, F, rec_d, n, p.samples, counters, cstride, prefix, queue, frames,
                                            ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "batch supersampling refine launch");
-    if (stats) {
-        RM_HIP(hipEventRecord(ctx->aa_ev2, ctx->stream));
-        RM_HIP(hipEventSynchronize(ctx->aa_ev2));
-        uint32_t total = 0;  // (the plan's sum of the counts, after the groups' total)
-        RM_HIP(hipMemcpy(&total, prefix + n + 1, sizeof(total), hipMemcpyDeviceToHost));
-        stats->refined = (int64_t)total;
-        RM_HIP(hipEventElapsedTime(&stats->detect_ms, ctx->ev0, ctx->ev1));
-        RM_HIP(hipEventElapsedTime(&stats->refine_ms, ctx->ev1, ctx->aa_ev2));
-    }
-    return RM_OK;
+    // (the count: the plan's sum of the views' counts, after the groups' total)
+    return stats ? refine_stats(ctx, prefix + n + 1, stats) : RM_OK;
 }
 
 // the checks of both calls, before any pointer is used, in the single calls' order
@@ -104,38 +81,26 @@ rm_status batch_aa_run(rm_ctx *ctx, const char *what, int W, int H, const rm_vie
         return fail(ctx, RM_ERR_INVALID_ARGUMENT, std::string(what) + ": host and device pointers mixed");
     const size_t px = (size_t)n * (size_t)W * (size_t)H, frame_bytes = px * sizeof(uint32_t);
     const size_t refined_bytes = (size_t)n * sizeof(uint32_t);
-    char *tmp = nullptr;  // host buffers: staged (frames | refined | mask)
-    if (!dev) RM_HIP(hipMalloc(&tmp, frame_bytes + (refined ? refined_bytes : 0) + (mask ? px : 0)));
-    uint32_t *frames_d = dev ? frames : reinterpret_cast<uint32_t *>(tmp);
-    uint32_t *refined_d = dev || !refined ? refined : reinterpret_cast<uint32_t *>(tmp + frame_bytes);
-    uint8_t *mask_d =
-        dev || !mask ? mask : reinterpret_cast<uint8_t *>(tmp + frame_bytes + (refined ? refined_bytes : 0));
+    Stage stage;  // host buffers: staged (frames | refined | mask)
+    if (!dev) {
+        stage.add(frames, frame_bytes, !render, true);
+        stage.add(refined, refined_bytes, false, true);
+        stage.add(mask, px, false, true);
+    }
+    rm_status st = stage.begin(ctx, "batch supersampling: staging");
+    uint32_t *frames_d = dev ? frames : stage.dev<uint32_t>(0);
+    uint32_t *refined_d = dev ? refined : stage.dev<uint32_t>(1);
+    uint8_t *mask_d = dev ? mask : stage.dev<uint8_t>(2);
     FrameConst F;
     const void *rec_d = nullptr;
-    rm_status st = batch_records(ctx, W, H, views, n, F, rec_d);
-    hipError_t e = hipSuccess;
+    if (st == RM_OK) st = batch_records(ctx, W, H, views, n, F, rec_d);
     if (st == RM_OK && render) {
         rm_stats base;
         st = batch_launch(ctx, F, rec_d, n, frames_d, true, stats ? &base : nullptr);
         if (st == RM_OK && stats) stats->base_ms = base.kernel_ms;
-    } else if (st == RM_OK && !dev) {
-        e = hipMemcpyAsync(frames_d, frames, frame_bytes, hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) st = hip_fail(ctx, e, "batch supersampling: staging");
     }
     if (st == RM_OK) st = refine_batch_dev(ctx, F, rec_d, n, *p, frames_d, mask_d, refined_d, stats);
-    if (!dev) {
-        if (st == RM_OK) {
-            e = hipMemcpyAsync(frames, frames_d, frame_bytes, hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess && refined)
-                e = hipMemcpyAsync(refined, refined_d, refined_bytes, hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess && mask) e = hipMemcpyAsync(mask, mask_d, px, hipMemcpyDeviceToHost, ctx->stream);
-            if (e != hipSuccess) st = hip_fail(ctx, e, "batch supersampling: staging");
-        }
-        e = hipStreamSynchronize(ctx->stream);  // (also after a failure: tmp may be in use)
-        if (st == RM_OK && e != hipSuccess) st = hip_fail(ctx, e, what);
-        (void)hipFree(tmp);
-    }
-    return st;
+    return stage.end(ctx, st, what);
 }
 
 }  // namespace

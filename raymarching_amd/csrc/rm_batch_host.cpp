@@ -39,22 +39,6 @@ rm_status batch_host_block(rm_ctx *ctx, size_t bytes, rm_ctx::BatchSlot *&slot) 
     return RM_OK;
 }
 
-// The device buffer for n records on the context's stream.  One buffer per
-// context (bloom's rule, as rm_aa_host.cpp aa_scratch): a batch on another
-// stream than the last one first waits, on the device, for that one, marked
-// when the context left its stream (rm_ctx_streams.cpp set_stream).
-rm_status batch_scratch(rm_ctx *ctx, size_t bytes) {
-    if (ctx->batch_ev && ctx->batch_stream != ctx->stream) RM_HIP(hipStreamWaitEvent(ctx->stream, ctx->batch_ev, 0));
-    if (bytes > ctx->batch_bytes) {
-        if (ctx->batch_views) RM_HIP(hipFree(ctx->batch_views));  // (waits for the launches that use it)
-        ctx->batch_views = nullptr;
-        ctx->batch_bytes = 0;
-        RM_HIP(hipMalloc(&ctx->batch_views, bytes));
-        ctx->batch_bytes = bytes;
-    }
-    return RM_OK;
-}
-
 }  // namespace
 
 namespace rmhost {
@@ -97,13 +81,13 @@ rm_status batch_records(rm_ctx *ctx, int W, int H, const rm_view *views, int n, 
         }
     }
     F.near_r = V.near_r;  // (shared by the views: pose_const withdraws the ladder's radius if any view's pose asks it)
-    if (rm_status st = batch_scratch(ctx, bytes)) return st;
-    rec_d = ctx->batch_views;
-    RM_HIP(hipMemcpyAsync(ctx->batch_views, slot->host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    rm_ctx::Scratch &sc = ctx->scratch[rm_ctx::kScratchBatch];  // the device buffer for n records
+    if (rm_status st = scratch_acquire(ctx, sc, bytes)) return st;
+    rec_d = sc.ptr;
+    RM_HIP(hipMemcpyAsync(sc.ptr, slot->host, bytes, hipMemcpyHostToDevice, ctx->stream));
     RM_HIP(hipEventRecord(slot->copied, ctx->stream));
     slot->used = true;
-    ctx->batch_stream = ctx->stream;
-    ctx->batch_pending = true;
+    scratch_used(ctx, sc);
     mark_done(ctx);
     return RM_OK;
 }

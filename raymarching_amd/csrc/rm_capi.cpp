@@ -1,17 +1,16 @@
 // rm_capi.cpp -- the C ABI declared in include/rm.h: the entry points, their
 // argument checks and messages.  The context is rm_ctx.h; a render launch is
 // rm_render_host.cpp, stream and event lifetime rm_ctx_streams.cpp, scene-file
-// text rm_scene_file.cpp.
+// text rm_scene_file.cpp; the post passes are rm_post_host.cpp.
 #include <cstdio>
 #include <cstring>
 #include <fstream>
-#include <initializer_list>
 #include <string>
 
 #include "rm_ctx.h"
 #include "rm_internal.h"
 #include "rm_scene_file.h"
-#include "rm_trace.h"
+#include "rm_stage.h"
 
 using rm::cycle_part;
 using rm::FrameConst;
@@ -25,18 +24,6 @@ static_assert(rmscene::kSceneS0 == rm::SCENE_S0 && rmscene::kSceneT == rm::SCENE
               "rm_scene_file.h restates rm::SceneId");
 
 namespace {
-
-// The tail of a launch-only entry point, after its argument checks:
-// launch() enqueues on the ctx stream, `what` names it in the error text.
-// (Inlined: the frame loops count host microseconds per call)
-template <class Launch>
-__attribute__((always_inline)) inline rm_status launch_on(rm_ctx *ctx, const char *what, Launch launch) {
-    RM_HIP(hipSetDevice(ctx->device));
-    hipError_t e = launch();
-    if (e != hipSuccess) return hip_fail(ctx, e, what);
-    mark_done(ctx);
-    return RM_OK;
-}
 
 // The compressed wire's one size rule (include/rm.h), checked by every entry
 // point that sizes, writes or reads a message before it touches a pointer: a
@@ -99,15 +86,8 @@ rm_status rm_destroy(rm_ctx *ctx) {
         if (b.last) (void)hipEventDestroy(b.last);
     }
     if (ctx->staging) (void)hipFree(ctx->staging);
-    if (ctx->mips) (void)hipFree(ctx->mips);
-    if (ctx->bloom_ev) (void)hipEventDestroy(ctx->bloom_ev);
-    if (ctx->aa_queue) (void)hipFree(ctx->aa_queue);
-    if (ctx->aa_ev) (void)hipEventDestroy(ctx->aa_ev);
+    for (rm_ctx::Scratch &sc : ctx->scratch) scratch_free(sc);
     if (ctx->aa_ev2) (void)hipEventDestroy(ctx->aa_ev2);
-    if (ctx->baa_scratch) (void)hipFree(ctx->baa_scratch);
-    if (ctx->baa_ev) (void)hipEventDestroy(ctx->baa_ev);
-    if (ctx->batch_views) (void)hipFree(ctx->batch_views);
-    if (ctx->batch_ev) (void)hipEventDestroy(ctx->batch_ev);
     for (auto &b : ctx->batch_slot) {  // (wait_idle above: no upload still reads a block)
         if (b.host) (void)hipHostFree(b.host);
         if (b.copied) (void)hipEventDestroy(b.copied);
@@ -637,115 +617,6 @@ rm_status rm_pack_rgba8(rm_ctx *ctx, int64_t npixels, const float *in, uint32_t 
     });
 }
 
-rm_status rm_fxaa(rm_ctx *ctx, int W, int H, const uint32_t *in, uint32_t *out) {
-    if (!ctx) return RM_ERR_INVALID_ARGUMENT;
-    if (!in || !out || W <= 0 || H <= 0 || in == out) return fail(ctx, RM_ERR_INVALID_ARGUMENT, "rm_fxaa: bad arguments");
-    if ((int64_t)W * H >= ((int64_t)1 << 30))  // the kernel's 32-bit byte offsets
-        return fail(ctx, RM_ERR_INVALID_ARGUMENT, "rm_fxaa: frame of 2^30 texels or more");
-    if (!is_device_ptr(in) || !is_device_ptr(out))
-        return fail(ctx, RM_ERR_INVALID_ARGUMENT, "rm_fxaa: device pointers required");
-    return launch_on(ctx, "fxaa launch", [&] {
-        rm::TraceRange range("rm_fxaa");
-        return rm::launch_fxaa(in, out, W, H, ctx->stream);
-    });
-}
-
-rm_status rm_bloom(rm_ctx *ctx, int W, int H, const uint32_t *in, uint32_t *out) {
-    if (!ctx) return RM_ERR_INVALID_ARGUMENT;
-    if (!in || !out || W <= 0 || H <= 0 || in == out)
-        return fail(ctx, RM_ERR_INVALID_ARGUMENT, "rm_bloom: bad arguments");
-    if (!is_device_ptr(in) || !is_device_ptr(out))
-        return fail(ctx, RM_ERR_INVALID_ARGUMENT, "rm_bloom: device pointers required");
-    RM_HIP(hipSetDevice(ctx->device));
-    rm::TraceRange range("rm_bloom");
-    const rm::BloomPlan plan = rm::bloom_plan(W, H);
-    bool cached = false;
-    if (rm_status st = bloom_scratch(ctx, plan.texels, W, H, cached)) return st;
-    hipError_t e = rm::launch_bloom(in, out, ctx->mips, plan, ctx->stream, cached);
-    if (e != hipSuccess) return hip_fail(ctx, e, "bloom launch");
-    bloom_done(ctx, W, H);
-    mark_done(ctx);
-    return RM_OK;
-}
-
-rm_status rm_post_chain(rm_ctx *ctx, int W, int H, const uint32_t *in, uint32_t *mid, uint32_t *out) {
-    if (!ctx) return RM_ERR_INVALID_ARGUMENT;
-    if (!in || !mid || !out || W <= 0 || H <= 0 || in == mid || mid == out || in == out)
-        return fail(ctx, RM_ERR_INVALID_ARGUMENT, "rm_post_chain: bad arguments");
-    if ((int64_t)W * H >= ((int64_t)1 << 30))  // the FXAA kernel's 32-bit byte offsets
-        return fail(ctx, RM_ERR_INVALID_ARGUMENT, "rm_post_chain: frame of 2^30 texels or more");
-    if (!is_device_ptr(in) || !is_device_ptr(mid) || !is_device_ptr(out))
-        return fail(ctx, RM_ERR_INVALID_ARGUMENT, "rm_post_chain: device pointers required");
-    RM_HIP(hipSetDevice(ctx->device));
-    rm::TraceRange range("rm_post_chain");
-    const rm::BloomPlan plan = rm::bloom_plan(W, H);
-    bool cached = false;
-    if (rm_status st = bloom_scratch(ctx, plan.texels, W, H, cached)) return st;
-    // main.cpp:209-214: FXAA into postTexture, its mip chain, bloom of it
-    // (the mips from FXAA's registers measured slower)
-    hipError_t e = rm::launch_fxaa(in, mid, W, H, ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "post chain: fxaa launch");
-    e = rm::launch_bloom(mid, out, ctx->mips, plan, ctx->stream, cached);
-    if (e != hipSuccess) return hip_fail(ctx, e, "post chain: bloom launch");
-    bloom_done(ctx, W, H);
-    mark_done(ctx);
-    return RM_OK;
-}
-
-static_assert(RM_POST_SAMPLE_FXAA == rm::kSampleFxaa && RM_POST_SAMPLE_TEXEL == rm::kSampleTexel &&
-                  RM_POST_SAMPLE_CHROMATIC == rm::kSampleChromatic && RM_POST_SAMPLE_CHROMATIC + 1 == rm::kSampleCount,
-              "rm_post_sample and the kernels' kSample*");
-static_assert(RM_TONEMAP_NONE == rm::kTonemapNone && RM_TONEMAP_ACES == rm::kTonemapAces &&
-                  RM_TONEMAP_REINHARD == rm::kTonemapReinhard && RM_TONEMAP_REINHARD_JODIE == rm::kTonemapJodie &&
-                  RM_TONEMAP_UNCHARTED2 == rm::kTonemapUncharted2 && RM_TONEMAP_UNCHARTED2 + 1 == rm::kTonemapCount,
-              "rm_tonemap and the kernels' kTonemap*");
-
-// what rm_post_frag and rm_post_chain_ex check alike (`who` names the call)
-static rm_status post_frag_args(rm_ctx *ctx, const char *who, int W, int H, int sample, int tonemap, bool distinct,
-                                std::initializer_list<const uint32_t *> bufs) {
-    auto bad = [&](const char *what) { return fail(ctx, RM_ERR_INVALID_ARGUMENT, std::string(who) + ": " + what); };
-    for (const uint32_t *p : bufs)
-        if (!p) return bad("bad arguments");
-    if (W <= 0 || H <= 0 || !distinct) return bad("bad arguments");
-    if (sample < 0 || sample >= rm::kSampleCount) return bad("unknown sample (rm_post_sample)");
-    if (tonemap < 0 || tonemap >= rm::kTonemapCount) return bad("unknown tonemap (rm_tonemap)");
-    if ((int64_t)W * H >= ((int64_t)1 << 30))  // the kernels' 32-bit byte offsets
-        return bad("frame of 2^30 texels or more");
-    for (const uint32_t *p : bufs)
-        if (!is_device_ptr(p)) return bad("device pointers required");
-    return RM_OK;
-}
-
-rm_status rm_post_frag(rm_ctx *ctx, int W, int H, int sample, int tonemap, const uint32_t *in, uint32_t *out) {
-    if (!ctx) return RM_ERR_INVALID_ARGUMENT;
-    if (rm_status st = post_frag_args(ctx, "rm_post_frag", W, H, sample, tonemap, in != out, {in, out})) return st;
-    return launch_on(ctx, "post_frag launch", [&] {
-        rm::TraceRange range("rm_post_frag");
-        return rm::launch_post_frag(in, out, W, H, sample, tonemap, ctx->stream);
-    });
-}
-
-rm_status rm_post_chain_ex(rm_ctx *ctx, int W, int H, int sample, int tonemap, const uint32_t *in, uint32_t *mid,
-                           uint32_t *out) {
-    if (!ctx) return RM_ERR_INVALID_ARGUMENT;
-    if (rm_status st = post_frag_args(ctx, "rm_post_chain_ex", W, H, sample, tonemap,
-                                      in != mid && mid != out && in != out, {in, mid, out}))
-        return st;
-    RM_HIP(hipSetDevice(ctx->device));
-    rm::TraceRange range("rm_post_chain_ex");
-    const rm::BloomPlan plan = rm::bloom_plan(W, H);
-    bool cached = false;
-    if (rm_status st = bloom_scratch(ctx, plan.texels, W, H, cached)) return st;
-    // main.cpp:209-214 with the edited post.frag: the pass into postTexture, bloom of it
-    hipError_t e = rm::launch_post_frag(in, mid, W, H, sample, tonemap, ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "post chain: post_frag launch");
-    e = rm::launch_bloom(mid, out, ctx->mips, plan, ctx->stream, cached);
-    if (e != hipSuccess) return hip_fail(ctx, e, "post chain: bloom launch");
-    bloom_done(ctx, W, H);
-    mark_done(ctx);
-    return RM_OK;
-}
-
 // rm_scene_eval and rm_scene_eval_form.  RM_FORM_EXACT launches rm_scene_eval's
 // kernel (and, for aux alone, the probe kernel without its other outputs).
 static rm_status scene_eval_form(rm_ctx *ctx, const float *points, int64_t n, int form, float *dist, float *material,
@@ -760,38 +631,37 @@ static rm_status scene_eval_form(rm_ctx *ctx, const float *points, int64_t n, in
                                                            "(#define RM_PLUGIN_EVAL_PROBE in the scene source)");
     if (n == 0) return RM_OK;
     RM_HIP(hipSetDevice(ctx->device));
-    // device views of the four buffers (host ones are staged)
+    // device views of the four buffers (host ones are staged, each on its own: the call takes a mixture)
     const size_t pb = (size_t)n * 3 * sizeof(float), db = (size_t)n * sizeof(float), mb = (size_t)n * 16 * sizeof(float);
-    const bool dp = is_device_ptr(points), dd = is_device_ptr(dist), dm = !material || is_device_ptr(material),
-               da = !aux || is_device_ptr(aux);
-    char *tmp = nullptr;
-    if (!(dp && dd && dm && da)) RM_HIP(hipMalloc(&tmp, pb + db + (material ? mb : 0) + (aux ? db : 0)));
-    const float *p = dp ? points : reinterpret_cast<float *>(tmp);
-    float *d = dd ? dist : reinterpret_cast<float *>(tmp + pb);
-    float *m = !material ? nullptr : dm ? material : reinterpret_cast<float *>(tmp + pb + db);
-    float *a = !aux ? nullptr : da ? aux : reinterpret_cast<float *>(tmp + pb + db + (material ? mb : 0));
+    Stage stage;
+    auto view = [&](const float *buf, size_t bytes, bool in) {
+        return !buf || is_device_ptr(buf) ? -1 : stage.add(buf, bytes, in, !in);
+    };
+    const int ip = view(points, pb, true), id = view(dist, db, false), im = view(material, mb, false),
+              ia = view(aux, db, false);
+    rm_status st = stage.begin(ctx, what);
+    const float *p = ip < 0 ? points : stage.dev<float>(ip);
+    float *d = id < 0 ? dist : stage.dev<float>(id);
+    float *m = im < 0 ? material : stage.dev<float>(im);
+    float *a = ia < 0 ? aux : stage.dev<float>(ia);
     hipError_t e = hipSuccess;
-    if (!dp) e = hipMemcpyAsync(const_cast<float *>(p), points, pb, hipMemcpyHostToDevice, ctx->stream);
     FrameConst F = frame_const(ctx, 1, 1, RowPart{1, 0, 1}, 1);
     auto probe = [&](int f, float *pd, float *pm) {
         return plugin ? rmplugin::launch_eval_probe(ctx->plugin, F, ctx->uniform_values, p, n, pd, pm, a, ctx->stream)
                       : rm::launch_scene_eval_form(ctx->scene, F, p, n, f, pd, pm, a, ctx->stream);
     };
-    if (e == hipSuccess && form == RM_FORM_EXACT) {
+    if (st == RM_OK && form == RM_FORM_EXACT) {
         e = plugin ? rmplugin::launch_eval(ctx->plugin, F, ctx->uniform_values, p, n, d, m, ctx->stream)
                    : rm::launch_scene_eval(ctx->scene, F, p, n, d, m, ctx->stream);
         if (e == hipSuccess && a)  // (a plugin's aux is 0)
             e = plugin ? hipMemsetAsync(a, 0, db, ctx->stream) : probe(RM_FORM_PROBE, nullptr, nullptr);
-    } else if (e == hipSuccess) {
+    } else if (st == RM_OK) {
         e = probe(form, d, m);
     }
-    if (e == hipSuccess && !dd) e = hipMemcpyAsync(dist, d, db, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && material && !dm) e = hipMemcpyAsync(material, m, mb, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && aux && !da) e = hipMemcpyAsync(aux, a, db, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (tmp) (void)hipFree(tmp);
-    if (e != hipSuccess) return hip_fail(ctx, e, what);
-    return RM_OK;
+    if (e != hipSuccess) st = hip_fail(ctx, e, what);
+    if (stage.staged()) return stage.end(ctx, st, what);
+    if (st == RM_OK) e = hipStreamSynchronize(ctx->stream);  // (device buffers: the call waits all the same)
+    return e != hipSuccess && st == RM_OK ? hip_fail(ctx, e, what) : st;
 }
 
 rm_status rm_scene_eval(rm_ctx *ctx, const float *points, int64_t n, float *dist, float *material) {

@@ -1,7 +1,8 @@
 // rm_ctx.h -- the context behind the C ABI (include/rm.h) and what the host
 // files of librm.so share about it: rm_capi.cpp (entry points),
 // rm_render_host.cpp (a render launch), rm_ctx_streams.cpp (stream and event
-// lifetime).  Internal; other translation units go through rm_internal.h.
+// lifetime, the scratch buffers' stream rule); the staging of host buffers is
+// rm_stage.h.  Internal; other translation units go through rm_internal.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -65,42 +66,37 @@ struct rm_ctx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float4 *staging = nullptr;
     size_t staging_bytes = 0;
-    uint32_t *mips = nullptr;  // bloom's mip levels 1..d2
-    size_t mips_texels = 0;
-    int bloom_runs_w = 0, bloom_runs_h = 0;  // the size whose bloom run tables `mips` holds (0: none)
+    // Device scratch buffers, one per use and context, grown on demand and shared by the context's streams:
+    // `stream` is the one of the last use (scratch_used); when the context leaves it (set_stream), `ev` is recorded
+    // there, and a use on another stream first waits, on the device, for that event (scratch_acquire) -- no marker
+    // per frame; one per leave, and only after a use (`pending`: used on `stream` since `ev` was last recorded)
+    struct Scratch {
+        void *ptr = nullptr;
+        size_t bytes = 0;
+        hipEvent_t ev = nullptr;  // made on the first leave that needs it
+        hipStream_t stream = nullptr;
+        bool pending = false;
+        template <class T>
+        T *as() const { return static_cast<T *>(ptr); }
+    };
+    enum ScratchId {
+        kScratchBloom,    // bloom's mip levels 1..d2, run tables and polynomials (rm_post_host.cpp)
+        kScratchAa,       // adaptive supersampling's queue: the count's line, then a word per pixel (rm_aa.h)
+        kScratchBatch,    // the device copy of a view batch's per-view records (rm_batch.h ViewConst)
+        kScratchBatchAa,  // a batch's supersampling: the counters, the plan and the queue (rm_batch_aa_plan.h)
+        kScratchCount
+    };
+    Scratch scratch[kScratchCount];
+    int bloom_runs_w = 0, bloom_runs_h = 0;  // the size whose bloom run tables the bloom scratch holds (0: none)
     hipStream_t bloom_runs_stream = nullptr;
-    // the scratch buffer is shared by the context's streams: when the context
-    // leaves the stream of its last bloom / post chain (bloom_stream), bloom_ev
-    // is recorded there, and a bloom on another stream first waits for it (no
-    // marker per frame; one per leave, and only after a bloom)
-    hipEvent_t bloom_ev = nullptr;
-    hipStream_t bloom_stream = nullptr;
-    bool bloom_pending = false;  // a bloom ran on bloom_stream since bloom_ev was last recorded
-    // rm_set_post_batch_scratch_limit: the most of `mips` a batched bloom may ask for (0: the default,
+    // rm_set_post_batch_scratch_limit: the most of the bloom scratch a batched bloom may ask for (0: the default,
     // rm_post_batch_plan.h); the batch's views go through the buffer in groups that fit
     int64_t post_batch_limit = 0;
-    // adaptive supersampling's queue (rm_aa.h: the count's line, then a word per
-    // pixel): one per context, grown on demand, with bloom's stream rule -- aa_ev
-    // is recorded when the context leaves the stream of its last refine, and a
-    // refine on another stream first waits for it
-    uint32_t *aa_queue = nullptr;
-    size_t aa_words = 0;
-    hipEvent_t aa_ev = nullptr;
-    hipStream_t aa_stream = nullptr;
-    bool aa_pending = false;
     hipEvent_t aa_ev2 = nullptr;  // a third timing event (rm_aa_stats: detect | refine), made on first use
-    // view batches (rm_batch_host.cpp): the device copy of a batch's per-view records (rm_batch.h ViewConst), one
-    // buffer per context, grown on demand, with bloom's stream rule -- batch_ev is recorded when the context
-    // leaves the stream of its last batch, and a batch on another stream first waits for it
-    void *batch_views = nullptr;
-    size_t batch_bytes = 0;
-    hipEvent_t batch_ev = nullptr;
-    hipStream_t batch_stream = nullptr;
-    bool batch_pending = false;
-    // ... and the host side of their upload: pinned blocks taken in turn, each with the event recorded after its
-    // asynchronous copy.  A call fills a block only once that event has completed, so a batch enqueued while the
-    // one before it still runs never overwrites records a copy has yet to read (at most kBatchSlots uploads in
-    // flight; the next call waits for the oldest copy, not for its kernel's frames)
+    // the host side of a view batch's record upload (rm_batch_host.cpp): pinned blocks taken in turn, each with the
+    // event recorded after its asynchronous copy.  A call fills a block only once that event has completed, so a
+    // batch enqueued while the one before it still runs never overwrites records a copy has yet to read (at most
+    // kBatchSlots uploads in flight; the next call waits for the oldest copy, not for its kernel's frames)
     struct BatchSlot {
         void *host = nullptr;
         size_t bytes = 0;
@@ -110,13 +106,6 @@ struct rm_ctx {
     static constexpr int kBatchSlots = 4;
     BatchSlot batch_slot[kBatchSlots];
     int batch_next = 0;
-    // adaptive supersampling of a view batch (rm_batch_aa_host.cpp): the counters, the plan and the queue
-    // (rm_batch_aa_plan.h layout), one buffer per context, grown on demand, with bloom's stream rule as above
-    uint32_t *baa_scratch = nullptr;
-    size_t baa_words = 0;
-    hipEvent_t baa_ev = nullptr;
-    hipStream_t baa_stream = nullptr;
-    bool baa_pending = false;
     // FrameConst.rcp_* of scenes S0/T (rm_render_host.cpp frame_rcp): the device's reciprocals of the frame
     // size and of u_resolution.y, kept per resolution -- the key changes when a window is resized, not per frame
     // (u_time and the pose do not enter it).  A small fixed-size cache, least recently used out, so that callers
@@ -217,12 +206,30 @@ inline bool is_device_ptr(const void *p) {
     return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
 }
 
+// The tail of a launch-only entry point, after its argument checks:
+// launch() enqueues on the ctx stream, `what` names it in the error text.
+// (Inlined: the frame loops count host microseconds per call)
+template <class Launch>
+__attribute__((always_inline)) inline rm_status launch_on(rm_ctx *ctx, const char *what, Launch launch) {
+    RM_HIP(hipSetDevice(ctx->device));
+    hipError_t e = launch();
+    if (e != hipSuccess) return hip_fail(ctx, e, what);
+    mark_done(ctx);
+    return RM_OK;
+}
+
 // ---- rm_ctx_streams.cpp
 rm_status persist_block(rm_ctx *ctx, rm_ctx::PersistBlock *&out);
 rm_ctx::Sched *sched_slot(rm_ctx *ctx, int W, int H, const rm::RowPart &part, int row0, int count, rm_status &st);
 hipError_t sched_release(rm_ctx *ctx, rm_ctx::Sched &e);
 rm_status set_stream(rm_ctx *ctx, hipStream_t s);  // rm_set_stream
-void wait_idle(rm_ctx *ctx);                       // rm_destroy: nothing the context enqueued still runs
+// A scratch buffer (rm_ctx::Scratch) of at least `bytes` on the context's stream: after the event of a last use on
+// another stream, and grown if it is too small (*grown: the old buffer and its contents are gone; a failed
+// allocation leaves the scratch empty).  scratch_used: work that uses it was enqueued on the context's stream
+rm_status scratch_acquire(rm_ctx *ctx, rm_ctx::Scratch &sc, size_t bytes, bool *grown = nullptr);
+void scratch_used(rm_ctx *ctx, rm_ctx::Scratch &sc);
+void scratch_free(rm_ctx::Scratch &sc);  // rm_destroy
+void wait_idle(rm_ctx *ctx);             // rm_destroy: nothing the context enqueued still runs
 
 // ---- rm_render_host.cpp
 int pick_kernel(const rm_params &p);
@@ -278,12 +285,9 @@ rm_status batch_ex_blocks(rm_ctx *ctx, const BatchEx &ex, int n, std::vector<uin
 // the loaded plugin's batch kernel, compiled and loaded if it is not yet
 rm_status batch_ex_ready(rm_ctx *ctx);
 
-// ---- rm_post_batch_host.cpp
-// bloom's scratch (ctx->mips: mip levels, run tables, polynomials) holds at least `words` on the context's stream,
-// for rm_bloom, the post chains and their batch forms alike; `cached`: its run tables are W x H's already (the
-// last bloom of this context had the same size and stream, and the buffer is the same).  bloom_done: a bloom of
-// W x H was enqueued on the stream, its run tables at bloom_plan(W, H)'s offsets
-rm_status bloom_scratch(rm_ctx *ctx, size_t words, int W, int H, bool &cached);
-void bloom_done(rm_ctx *ctx, int W, int H);
+// ---- rm_aa_host.cpp
+// the stats tail of a refine and of a batch's (rm_batch_aa_host.cpp): aa_ev2 recorded and waited for, the device
+// word at `count` into stats->refined, detect_ms = ev0..ev1 and refine_ms = ev1..aa_ev2
+rm_status refine_stats(rm_ctx *ctx, const uint32_t *count, rm_aa_stats *stats);
 
 }  // namespace rmhost

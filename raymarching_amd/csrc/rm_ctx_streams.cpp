@@ -1,6 +1,7 @@
 // rm_ctx_streams.cpp -- stream and event lifetime of a context (rm_ctx.h): the
 // bookkeeping that lets it leave a stream without a marker per frame, and wait
-// for its own work alone when buffers are released or it is destroyed.
+// for its own work alone when buffers are released or it is destroyed; and the
+// one rule by which its scratch buffers pass from stream to stream.
 #include "rm_ctx.h"
 
 namespace rmhost {
@@ -182,35 +183,39 @@ rm_ctx::Sched *sched_slot(rm_ctx *ctx, int W, int H, const rm::RowPart &part, in
     return lru;
 }
 
+rm_status scratch_acquire(rm_ctx *ctx, rm_ctx::Scratch &sc, size_t bytes, bool *grown) {
+    if (sc.ev && sc.stream != ctx->stream) RM_HIP(hipStreamWaitEvent(ctx->stream, sc.ev, 0));
+    if (bytes > sc.bytes) {
+        if (sc.ptr) RM_HIP(hipFree(sc.ptr));  // (waits for the launches that use it)
+        sc.ptr = nullptr;
+        sc.bytes = 0;
+        if (grown) *grown = true;
+        RM_HIP(hipMalloc(&sc.ptr, bytes));
+        sc.bytes = bytes;
+    }
+    return RM_OK;
+}
+
+void scratch_used(rm_ctx *ctx, rm_ctx::Scratch &sc) {
+    sc.stream = ctx->stream;
+    sc.pending = true;
+}
+
+void scratch_free(rm_ctx::Scratch &sc) {
+    if (sc.ptr) (void)hipFree(sc.ptr);
+    if (sc.ev) (void)hipEventDestroy(sc.ev);
+    sc = rm_ctx::Scratch();
+}
+
 rm_status set_stream(rm_ctx *ctx, hipStream_t s) {
-    if (s != ctx->stream && ctx->bloom_pending && ctx->bloom_stream == ctx->stream) {
-        // the last bloom's scratch use, marked for a bloom on another stream (bloom_scratch)
-        RM_HIP(hipSetDevice(ctx->device));
-        if (!ctx->bloom_ev) RM_HIP(hipEventCreateWithFlags(&ctx->bloom_ev, hipEventDisableTiming));
-        RM_HIP(hipEventRecord(ctx->bloom_ev, ctx->stream));
-        ctx->bloom_pending = false;
-    }
-    if (s != ctx->stream && ctx->aa_pending && ctx->aa_stream == ctx->stream) {
-        // the same for the last refine's queue (rm_aa_host.cpp aa_scratch)
-        RM_HIP(hipSetDevice(ctx->device));
-        if (!ctx->aa_ev) RM_HIP(hipEventCreateWithFlags(&ctx->aa_ev, hipEventDisableTiming));
-        RM_HIP(hipEventRecord(ctx->aa_ev, ctx->stream));
-        ctx->aa_pending = false;
-    }
-    if (s != ctx->stream && ctx->batch_pending && ctx->batch_stream == ctx->stream) {
-        // the same for the last view batch's records (rm_batch_host.cpp batch_scratch)
-        RM_HIP(hipSetDevice(ctx->device));
-        if (!ctx->batch_ev) RM_HIP(hipEventCreateWithFlags(&ctx->batch_ev, hipEventDisableTiming));
-        RM_HIP(hipEventRecord(ctx->batch_ev, ctx->stream));
-        ctx->batch_pending = false;
-    }
-    if (s != ctx->stream && ctx->baa_pending && ctx->baa_stream == ctx->stream) {
-        // the same for the last batch supersampling's scratch (rm_batch_aa_host.cpp batch_aa_scratch)
-        RM_HIP(hipSetDevice(ctx->device));
-        if (!ctx->baa_ev) RM_HIP(hipEventCreateWithFlags(&ctx->baa_ev, hipEventDisableTiming));
-        RM_HIP(hipEventRecord(ctx->baa_ev, ctx->stream));
-        ctx->baa_pending = false;
-    }
+    for (rm_ctx::Scratch &sc : ctx->scratch)
+        if (sc.pending && s != ctx->stream && sc.stream == ctx->stream) {
+            // a scratch's last use, marked for a use on another stream (scratch_acquire); a kept stream too
+            RM_HIP(hipSetDevice(ctx->device));
+            if (!sc.ev) RM_HIP(hipEventCreateWithFlags(&sc.ev, hipEventDisableTiming));
+            RM_HIP(hipEventRecord(sc.ev, ctx->stream));
+            sc.pending = false;
+        }
 #ifdef RM_ANALYSIS_LEAVE_NO_RECORD
     // analysis builds only (-DRM_ANALYSIS_LEAVE_NO_RECORD, tools/scale_model.py
     // prices the marker with it; unsafe: a later release of a schedule buffer or

@@ -21,6 +21,7 @@
 #include <cctype>
 #include <cstdlib>
 #include <fstream>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 
@@ -330,53 +331,67 @@ void unload(Module& m) {
     m = Module();
 }
 
-bool batch_ready(Module& m, std::string& err, hipError_t& e) {
+namespace {
+
+std::string load_error(const char* label, hipError_t e) {
+    return std::string("scene plugin ") + label + " module load: " + hipGetErrorString(e);
+}
+
+// A one-kernel form of m's scene: compiled (cached by text, as compile caches), loaded on the current device into
+// `mod`, its kernel looked up into `fn`; both stay null on failure
+bool form_ready(Module& m, Form form, const char* label, const char* kernel, hipModule_t& mod, hipFunction_t& fn,
+                std::string& err, hipError_t& e) {
     e = hipSuccess;
-    if (m.render_batch) return true;
     Code code;
     rmuniform::Table uniforms;
-    if (!compile(m.src, m.file, code, err, uniforms, FORM_BATCH)) return false;
-    hipModule_t mod = nullptr;
+    if (!compile(m.src, m.file, code, err, uniforms, form)) return false;
     e = hipModuleLoadData(&mod, code->data());
-    if (e == hipSuccess) {
-        e = hipModuleGetFunction(&m.render_batch, mod, "rm_plugin_render_batch");
-        if (e != hipSuccess) {
-            (void)hipModuleUnload(mod);
-            m.render_batch = nullptr;
-        }
-    }
-    if (e != hipSuccess) {
-        err = std::string("scene plugin batch module load: ") + hipGetErrorString(e);
-        return false;
-    }
-    m.batch_mod = mod;
-    return true;
+    if (e == hipSuccess && (e = hipModuleGetFunction(&fn, mod, kernel)) != hipSuccess) (void)hipModuleUnload(mod);
+    if (e == hipSuccess) return true;
+    mod = nullptr;
+    fn = nullptr;
+    err = load_error(label, e);
+    return false;
+}
+
+// One launch of a kernel of m's scene on a grid of `block`-thread workgroups.  Its arguments: F, then -- iff the
+// scene declares uniforms -- the uniform block, then `rest` (pointers to the values); a null F: the batch kernel,
+// which takes `rest` alone.  (The launch copies each argument by the size the kernel declares: the block's first
+// uniform_slots slots, read now -- a later rm_set_uniform* does not reach a launch already enqueued.)
+hipError_t launch(hipFunction_t fn, dim3 grid, unsigned block, const Module& m, const rm::FrameConst* F,
+                  const uint32_t* uniforms, hipStream_t s, std::initializer_list<const void*> rest) {
+    void* args[8];
+    int n = 0;
+    if (F) args[n++] = const_cast<rm::FrameConst*>(F);
+    if (F && m.uniform_slots > 0) args[n++] = const_cast<uint32_t*>(uniforms);
+    for (const void* a : rest) args[n++] = const_cast<void*>(a);
+    return hipModuleLaunchKernel(fn, grid.x, grid.y, grid.z, block, 1, 1, 0, s, args, nullptr);
+}
+
+}  // namespace
+
+bool batch_ready(Module& m, std::string& err, hipError_t& e) {
+    e = hipSuccess;
+    return m.render_batch ||
+           form_ready(m, FORM_BATCH, "batch", "rm_plugin_render_batch", m.batch_mod, m.render_batch, err, e);
 }
 
 bool aa_ready(Module& m, std::string& err, hipError_t& e) {
     e = hipSuccess;
     if (m.aa_refine) return true;
-    Code code;
-    rmuniform::Table uniforms;
-    if (!compile(m.src, m.file, code, err, uniforms, FORM_AA)) return false;
-    hipModule_t mod = nullptr;
-    hipFunction_t fn = nullptr;
+    if (!form_ready(m, FORM_AA, "AA", "rm_plugin_aa_refine", m.aa_mod, m.aa_refine, err, e)) return false;
+    // the grid, as rm_aa.h's launch_aa_refine_as fixes it: the one-wave workgroups the device holds at once
     int dev = 0, cus = 0, per_cu = 0;
-    e = hipModuleLoadData(&mod, code->data());
-    if (e == hipSuccess) {
-        e = hipModuleGetFunction(&fn, mod, "rm_plugin_aa_refine");
-        // the grid, as rm_aa.h's launch_aa_refine_as fixes it: the one-wave workgroups the device holds at once
-        if (e == hipSuccess) e = hipGetDevice(&dev);
-        if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (e == hipSuccess) e = hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, 0);
-        if (e != hipSuccess) (void)hipModuleUnload(mod);
-    }
+    e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e == hipSuccess) e = hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, m.aa_refine, 64, 0);
     if (e != hipSuccess) {
-        err = std::string("scene plugin AA module load: ") + hipGetErrorString(e);
+        (void)hipModuleUnload(m.aa_mod);
+        m.aa_mod = nullptr;
+        m.aa_refine = nullptr;
+        err = load_error("AA", e);
         return false;
     }
-    m.aa_mod = mod;
-    m.aa_refine = fn;
     m.aa_grid = (unsigned)std::max(1, cus * std::max(per_cu, 1));
     return true;
 }
@@ -384,27 +399,16 @@ bool aa_ready(Module& m, std::string& err, hipError_t& e) {
 hipError_t launch_aa_refine(const Module& m, const rm::FrameConst& F, const uint32_t* uniforms, int kshift,
                             const uint32_t* count, const uint32_t* queue, uint32_t* frame, hipStream_t s) {
     if (!m.aa_refine) return hipErrorInvalidDeviceFunction;
-    rm::FrameConst f = F;
-    int k = kshift;
-    const uint32_t *c = count, *q = queue;
-    uint32_t* o = frame;
-    // (the uniform block is read now, as launch_render's)
-    void* with_block[] = {&f, const_cast<uint32_t*>(uniforms), &k, &c, &q, &o};
-    void* args[] = {&f, &k, &c, &q, &o};
-    return hipModuleLaunchKernel(m.aa_refine, m.aa_grid, 1, 1, 64, 1, 1, 0, s, m.uniform_slots > 0 ? with_block : args,
-                                 nullptr);
+    return launch(m.aa_refine, dim3(m.aa_grid), 64, m, &F, uniforms, s, {&kshift, &count, &queue, &frame});
 }
 
 hipError_t launch_render_batch(const Module& m, const void* records, int W, int H, int n, void* out, bool rgba8,
                                hipStream_t s) {
     if (!m.render_batch) return hipErrorInvalidDeviceFunction;
     if (n <= 0) return hipSuccess;
-    const void* r = records;
-    void* o = out;
-    int r8 = rgba8 ? 1 : 0;
-    void* args[] = {&r, &o, &r8};
-    return hipModuleLaunchKernel(m.render_batch, (unsigned)((W + 7) / 8), (unsigned)((H + 7) / 8), (unsigned)n, 64, 1,
-                                 1, 0, s, args, nullptr);
+    const int r8 = rgba8 ? 1 : 0;
+    return launch(m.render_batch, dim3((unsigned)((W + 7) / 8), (unsigned)((H + 7) / 8), (unsigned)n), 64, m, nullptr,
+                  nullptr, s, {&records, &out, &r8});
 }
 
 hipError_t launch_render(const Module& m, const rm::FrameConst& F, const uint32_t* uniforms, void* out, bool rgba8,
@@ -412,75 +416,38 @@ hipError_t launch_render(const Module& m, const rm::FrameConst& F, const uint32_
     if (!m.render || !m.render_count) return hipErrorInvalidDeviceFunction;
     rm::FrameConst f = F;
     f.gx_magic = rm::div_magic((uint32_t)((F.W + 7) / 8), (uint64_t)((F.W + 7) / 8) * (uint64_t)((F.nrows + 7) / 8));
-    void* o = out;
-    int r8 = rgba8 ? 1 : 0;
-    unsigned long long* e = evals;
-    // (the launch copies each argument by the size the kernel declares: the
-    // block's first uniform_slots slots, read now -- a later rm_set_uniform*
-    // does not reach a launch already enqueued)
-    void* with_block[] = {&f, const_cast<uint32_t*>(uniforms), &o, &r8, &e};
-    void* args[] = {&f, &o, &r8, &e};
-    return hipModuleLaunchKernel(evals ? m.render_count : m.render, (unsigned)((F.W + 7) / 8),
-                                 (unsigned)((F.nrows + 7) / 8), 1, 64, 1, 1, 0, s,
-                                 m.uniform_slots > 0 ? with_block : args, nullptr);
+    const int r8 = rgba8 ? 1 : 0;
+    return launch(evals ? m.render_count : m.render, dim3((unsigned)((F.W + 7) / 8), (unsigned)((F.nrows + 7) / 8)), 64,
+                  m, &f, uniforms, s, {&out, &r8, &evals});
 }
 
 hipError_t launch_eval(const Module& m, const rm::FrameConst& F, const uint32_t* uniforms, const float* pts,
                        long long n, float* dist, float* mat, hipStream_t s) {
     if (n <= 0) return hipSuccess;
-    rm::FrameConst f = F;
-    const float* p = pts;
-    long long nn = n;
-    float* d = dist;
-    float* mm = mat;
-    void* with_block[] = {&f, const_cast<uint32_t*>(uniforms), &p, &nn, &d, &mm};
-    void* args[] = {&f, &p, &nn, &d, &mm};
-    return hipModuleLaunchKernel(m.eval, (unsigned)((n + 255) / 256), 1, 1, 256, 1, 1, 0, s,
-                                 m.uniform_slots > 0 ? with_block : args, nullptr);
+    return launch(m.eval, dim3((unsigned)((n + 255) / 256)), 256, m, &F, uniforms, s, {&pts, &n, &dist, &mat});
 }
 
 hipError_t launch_eval_probe(const Module& m, const rm::FrameConst& F, const uint32_t* uniforms, const float* pts,
                              long long n, float* dist, float* mat, float* aux, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     if (!m.eval_probe) return hipErrorInvalidDeviceFunction;
-    rm::FrameConst f = F;
-    const float* p = pts;
-    long long nn = n;
-    float* d = dist;
-    float* mm = mat;
-    float* a = aux;
-    // (the uniform block is read now, as launch_eval's)
-    void* with_block[] = {&f, const_cast<uint32_t*>(uniforms), &p, &nn, &d, &mm, &a};
-    void* args[] = {&f, &p, &nn, &d, &mm, &a};
-    return hipModuleLaunchKernel(m.eval_probe, (unsigned)((n + 255) / 256), 1, 1, 256, 1, 1, 0, s,
-                                 m.uniform_slots > 0 ? with_block : args, nullptr);
+    return launch(m.eval_probe, dim3((unsigned)((n + 255) / 256)), 256, m, &F, uniforms, s,
+                  {&pts, &n, &dist, &mat, &aux});
 }
 
 hipError_t launch_cast(const Module& m, const rm::FrameConst& F, const uint32_t* uniforms, const rm::RayQuery& Q,
                        int inside, int block, hipStream_t s) {
     if (Q.n <= 0) return hipSuccess;
     if (!m.cast) return hipErrorInvalidDeviceFunction;
-    rm::FrameConst f = F;
-    rm::RayQuery q = Q;
-    int in = inside;
-    // (the uniform block is read now, as launch_eval's)
-    void* with_block[] = {&f, const_cast<uint32_t*>(uniforms), &q, &in};
-    void* args[] = {&f, &q, &in};
-    return hipModuleLaunchKernel(m.cast, (unsigned)((Q.n + block - 1) / block), 1, 1, (unsigned)block, 1, 1, 0, s,
-                                 m.uniform_slots > 0 ? with_block : args, nullptr);
+    return launch(m.cast, dim3((unsigned)((Q.n + block - 1) / block)), (unsigned)block, m, &F, uniforms, s,
+                  {&Q, &inside});
 }
 
 hipError_t launch_shade(const Module& m, const rm::FrameConst& F, const uint32_t* uniforms, const rm::ShadeRays& Q,
                         hipStream_t s) {
     if (!m.shade) return hipErrorInvalidDeviceFunction;
     if (Q.n <= 0) return hipSuccess;
-    rm::FrameConst f = F;
-    rm::ShadeRays q = Q;
-    // (the uniform block is read now, as launch_eval's)
-    void* with_block[] = {&f, const_cast<uint32_t*>(uniforms), &q};
-    void* args[] = {&f, &q};
-    return hipModuleLaunchKernel(m.shade, rm::shade_grid(Q), 1, 1, 64, 1, 1, 0, s,
-                                 m.uniform_slots > 0 ? with_block : args, nullptr);
+    return launch(m.shade, dim3(rm::shade_grid(Q)), 64, m, &F, uniforms, s, {&Q});
 }
 
 }  // namespace rmplugin

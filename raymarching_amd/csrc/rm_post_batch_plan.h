@@ -3,7 +3,7 @@
 // size rule, what of bloom's scratch every view needs and what the views share,
 // how many views a group holds under a scratch limit, and how many kernel
 // launches a chain makes.  Shared by the host entry points
-// (rm_post_batch_host.cpp) and the launch code (rm_post_batch.hip), so that
+// (rm_post_host.cpp) and the launch code (rm_post_batch.hip), so that
 // rm_post_batch_plan reports what a call really allocates and launches.  Plain
 // C++ on the host, no HIP: tests/host/post_batch_plan_test.cpp includes this
 // header alone.

@@ -5,6 +5,7 @@
 
 #include "rm_ctx.h"
 #include "rm_rays.h"
+#include "rm_stage.h"
 #include "rm_trace.h"
 
 using rm::FrameConst;
@@ -77,43 +78,26 @@ rm_status rm_cast_rays(rm_ctx *ctx, const float *origins, int shared_origin, con
                          {out->steps, N * f, false},        {out->position, N * 3 * f, false},
                          {out->normal, N * 3 * f, false},   {out->material, N * 16 * f, false}};
     int ndev = 0, nused = 0;
-    size_t total = 0;
     for (const Buf &b : bufs) {
         if (!b.p) continue;
         nused++;
         ndev += is_device_ptr(b.p) ? 1 : 0;
-        total += (b.bytes + 255) & ~(size_t)255;
     }
     if (ndev != 0 && ndev != nused)
         return fail(ctx, RM_ERR_INVALID_ARGUMENT, "rm_cast_rays: host and device pointers mixed");
+    // host buffers: staged, and the call returns when the results are written
+    Stage stage;
+    void *dev[8];  // the buffers' device views
+    for (int k = 0; k < 8; k++) {
+        dev[k] = const_cast<void *>(bufs[k].p);
+        if (!ndev) stage.add(bufs[k].p, bufs[k].bytes, bufs[k].input, !bufs[k].input);
+    }
+    rm_status st = stage.begin(ctx, "rm_cast_rays: staging");
+    for (int k = 0; k < 8 && !ndev; k++) dev[k] = stage.dev<void>(k);
     rm::RayQuery Q;
     std::memset(&Q, 0, sizeof(Q));
     Q.n = n;
     Q.shared_origin = shared_origin ? 1 : 0;
-    if (ndev) {
-        Q.origins = origins;
-        Q.directions = directions;
-        Q.t = out->t;
-        Q.status = out->status;
-        Q.steps = out->steps;
-        Q.position = out->position;
-        Q.normal = out->normal;
-        Q.material = out->material;
-        return cast_dev(ctx, Q, inside, stats);
-    }
-    // host buffers: staged, and the call returns when the results are written
-    char *tmp = nullptr;
-    RM_HIP(hipMalloc(&tmp, total));
-    void *dev[8] = {};
-    size_t off = 0;
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < 8; k++) {
-        if (!bufs[k].p) continue;
-        dev[k] = tmp + off;
-        off += (bufs[k].bytes + 255) & ~(size_t)255;
-        if (bufs[k].input && e == hipSuccess)
-            e = hipMemcpyAsync(dev[k], bufs[k].p, bufs[k].bytes, hipMemcpyHostToDevice, ctx->stream);
-    }
     Q.origins = static_cast<const float *>(dev[0]);
     Q.directions = static_cast<const float *>(dev[1]);
     Q.t = static_cast<float *>(dev[2]);
@@ -122,16 +106,8 @@ rm_status rm_cast_rays(rm_ctx *ctx, const float *origins, int shared_origin, con
     Q.position = static_cast<float *>(dev[5]);
     Q.normal = static_cast<float *>(dev[6]);
     Q.material = static_cast<float *>(dev[7]);
-    rm_status st = e == hipSuccess ? cast_dev(ctx, Q, inside, stats) : hip_fail(ctx, e, "rm_cast_rays: staging");
-    for (int k = 2; k < 8 && st == RM_OK; k++) {
-        if (!bufs[k].p) continue;
-        e = hipMemcpyAsync(const_cast<void *>(bufs[k].p), dev[k], bufs[k].bytes, hipMemcpyDeviceToHost, ctx->stream);
-        if (e != hipSuccess) st = hip_fail(ctx, e, "rm_cast_rays: staging");
-    }
-    e = hipStreamSynchronize(ctx->stream);  // (also after a failure: tmp may be in use)
-    if (st == RM_OK && e != hipSuccess) st = hip_fail(ctx, e, "rm_cast_rays");
-    (void)hipFree(tmp);
-    return st;
+    if (st == RM_OK) st = cast_dev(ctx, Q, inside, stats);
+    return stage.end(ctx, st, "rm_cast_rays");
 }
 
 rm_status rm_camera_rays(rm_ctx *ctx, int W, int H, float *origin3, float *directions) {
@@ -151,23 +127,18 @@ rm_status rm_camera_rays(rm_ctx *ctx, int W, int H, float *origin3, float *direc
                       : ctx->scene == rm::SCENE_O  ? rm::ScenePolicy<rm::SCENE_O>::kHwMath
                       : ctx->scene == rm::SCENE_OG ? rm::ScenePolicy<rm::SCENE_OG>::kHwMath
                                                    : rm::ScenePolicy<rm::SCENE_PLUGIN>::kHwMath;
-    float *tmp = nullptr;
-    if (!dev_d) RM_HIP(hipMalloc(&tmp, bytes));
+    Stage stage;  // host directions: staged
+    if (!dev_d) stage.add(directions, bytes, false, true);
+    if (rm_status st = stage.begin(ctx, "rm_camera_rays")) return st;
     if (!dev_o) {
         origin3[0] = F.pos_x;
         origin3[1] = F.pos_y;
         origin3[2] = F.pos_z;
     }
-    hipError_t e = rm::launch_camera_rays(fast, F, dev_o ? origin3 : nullptr, dev_d ? directions : tmp, ctx->stream);
+    const hipError_t e = rm::launch_camera_rays(fast, F, dev_o ? origin3 : nullptr,
+                                                dev_d ? directions : stage.dev<float>(0), ctx->stream);
     if (e == hipSuccess) mark_done(ctx);
-    if (e == hipSuccess && !dev_d) e = hipMemcpyAsync(directions, tmp, bytes, hipMemcpyDeviceToHost, ctx->stream);
-    if (!dev_d) {
-        const hipError_t es = hipStreamSynchronize(ctx->stream);
-        if (e == hipSuccess) e = es;
-        (void)hipFree(tmp);
-    }
-    if (e != hipSuccess) return hip_fail(ctx, e, "rm_camera_rays");
-    return RM_OK;
+    return stage.end(ctx, e == hipSuccess ? RM_OK : hip_fail(ctx, e, "rm_camera_rays"), "rm_camera_rays");
 }
 
 }  // extern "C"

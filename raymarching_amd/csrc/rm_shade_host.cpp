@@ -5,6 +5,7 @@
 
 #include "rm_ctx.h"
 #include "rm_shade.h"
+#include "rm_stage.h"
 #include "rm_trace.h"
 
 using rm::FrameConst;
@@ -80,12 +81,10 @@ rm_status rm_shade_rays(rm_ctx *ctx, const float *origins, int shared_origin, co
                          {directions, N * 3 * f, true},
                          {out, out_rgba ? N * 4 * f : N * sizeof(uint32_t), false}};
     int ndev = 0, nused = 0;
-    size_t total = 0;
     for (const Buf &b : bufs) {
         if (!b.p) continue;
         nused++;
         ndev += is_device_ptr(b.p) ? 1 : 0;
-        total += (b.bytes + 255) & ~(size_t)255;
     }
     if (ndev != 0 && ndev != nused)
         return fail(ctx, RM_ERR_INVALID_ARGUMENT, "rm_shade_rays: host and device pointers mixed");
@@ -107,39 +106,21 @@ rm_status rm_shade_rays(rm_ctx *ctx, const float *origins, int shared_origin, co
     Q.width = params->width;
     Q.display = params->output == RM_SHADE_DISPLAY ? 1 : 0;
     Q.vignette = params->vignette;
-    if (ndev) {
-        Q.origins = shared_origin ? nullptr : origins;
-        Q.directions = directions;
-        Q.rgba = reinterpret_cast<float4 *>(out_rgba);
-        Q.rgba8 = out_rgba8;
-        return shade_dev(ctx, F, Q, stats);
-    }
     // host buffers: staged, and the call returns when the results are written
-    char *tmp = nullptr;
-    RM_HIP(hipMalloc(&tmp, total));
-    void *dev[3] = {};
-    size_t off = 0;
-    hipError_t e = hipSuccess;
+    Stage stage;
+    void *dev[3];  // the buffers' device views
     for (int k = 0; k < 3; k++) {
-        if (!bufs[k].p) continue;
-        dev[k] = tmp + off;
-        off += (bufs[k].bytes + 255) & ~(size_t)255;
-        if (bufs[k].input && e == hipSuccess)
-            e = hipMemcpyAsync(dev[k], bufs[k].p, bufs[k].bytes, hipMemcpyHostToDevice, ctx->stream);
+        dev[k] = const_cast<void *>(bufs[k].p);
+        if (!ndev) stage.add(bufs[k].p, bufs[k].bytes, bufs[k].input, !bufs[k].input);
     }
+    rm_status st = stage.begin(ctx, "rm_shade_rays: staging");
+    for (int k = 0; k < 3 && !ndev; k++) dev[k] = stage.dev<void>(k);
     Q.origins = static_cast<const float *>(dev[0]);
     Q.directions = static_cast<const float *>(dev[1]);
     Q.rgba = out_rgba ? static_cast<float4 *>(dev[2]) : nullptr;
     Q.rgba8 = out_rgba8 ? static_cast<uint32_t *>(dev[2]) : nullptr;
-    rm_status st = e == hipSuccess ? shade_dev(ctx, F, Q, stats) : hip_fail(ctx, e, "rm_shade_rays: staging");
-    if (st == RM_OK) {
-        e = hipMemcpyAsync(out, dev[2], bufs[2].bytes, hipMemcpyDeviceToHost, ctx->stream);
-        if (e != hipSuccess) st = hip_fail(ctx, e, "rm_shade_rays: staging");
-    }
-    e = hipStreamSynchronize(ctx->stream);  // (also after a failure: tmp may be in use)
-    if (st == RM_OK && e != hipSuccess) st = hip_fail(ctx, e, "rm_shade_rays");
-    (void)hipFree(tmp);
-    return st;
+    if (st == RM_OK) st = shade_dev(ctx, F, Q, stats);
+    return stage.end(ctx, st, "rm_shade_rays");
 }
 
 }  // extern "C"
