@@ -20,6 +20,7 @@ lower-level handle (one librm context) used by bench.py and the tests.
 from __future__ import annotations
 
 import ctypes
+import math
 import sys
 
 from . import _lib
@@ -134,7 +135,7 @@ class Renderer:
                    schedule=None) -> None:
         p = self.params()
         if schedule is not None:
-            p.schedule = {"adaptive": 1, "rowmajor": 0}.get(schedule, schedule)
+            p.schedule = _lib.named(schedule, _lib.SCHEDULES, "schedule")
         if max_steps is not None:
             p.max_steps = int(max_steps)
         if shadow_max_steps is not None:
@@ -142,7 +143,7 @@ class Renderer:
         if count_evals is not None:
             p.count_evals = int(bool(count_evals))
         if kernel is not None:
-            p.kernel = {"auto": 0, "tile16": 1, "tile8": 2, "tile16x4": 3, "persist": 4}.get(kernel, kernel)
+            p.kernel = _lib.named(kernel, _lib.KERNELS, "kernel")
         check(lib().rm_set_params(self._ctx, ctypes.byref(p)), self._ctx)
 
     def params(self) -> RmParams:
@@ -187,28 +188,29 @@ class Renderer:
     # --- passes ----------------------------------------------------------
     @staticmethod
     def _ptr(t):
+        if t is None:
+            return None
         return ctypes.c_void_p(t.data_ptr()) if hasattr(t, "data_ptr") else ctypes.c_void_p(t.ctypes.data)
+
+    def _steps(self, fn) -> int:
+        n = ctypes.c_uint64(0)
+        check(fn(self._ctx, ctypes.byref(n)), self._ctx)
+        return int(n.value)
 
     def certified_steps(self) -> int:
         """rm_certified_steps: of the last counted render's evals, the soft-shadow
         ray-steps scene T's certificate proves away; 0 elsewhere."""
-        n = ctypes.c_uint64(0)
-        check(lib().rm_certified_steps(self._ctx, ctypes.byref(n)), self._ctx)
-        return int(n.value)
+        return self._steps(lib().rm_certified_steps)
 
     def reflection_cleared_steps(self) -> int:
         """rm_reflection_cleared_steps: of the last counted render's evals, the reflection-march
         ray-steps scene T's reflection certificate proves away; 0 elsewhere."""
-        n = ctypes.c_uint64(0)
-        check(lib().rm_reflection_cleared_steps(self._ctx, ctypes.byref(n)), self._ctx)
-        return int(n.value)
+        return self._steps(lib().rm_reflection_cleared_steps)
 
     def near_sky_steps(self) -> int:
         """rm_near_sky_steps: of the last counted render's evals, the primary- and reflection-march ray-steps of
         scene T's waves that the near-sky ladder lets skip both marches; 0 elsewhere."""
-        n = ctypes.c_uint64(0)
-        check(lib().rm_near_sky_steps(self._ctx, ctypes.byref(n)), self._ctx)
-        return int(n.value)
+        return self._steps(lib().rm_near_sky_steps)
 
     def _stats(self, s) -> dict:
         """rm_stats as a dict, with `certified` (rm_certified_steps of the same call), `reflection_cleared`
@@ -217,16 +219,46 @@ class Renderer:
         return dict(s.as_dict(), certified=self.certified_steps(), reflection_cleared=self.reflection_cleared_steps(),
                     near_sky=self.near_sky_steps())
 
+    def _out(self, out, shape, dtype="int32", like=None):
+        """The caller's buffer after _check_out for `shape` 32-bit elements, or,
+        for None, a new tensor of that shape and dtype (a torch dtype or its
+        name; int32: RGBA8 words) on this renderer's device -- where `like`
+        lives, if given."""
+        if out is not None:
+            _check_out(out, math.prod(shape))
+            return out
+        torch = _torch()
+        return torch.empty(shape, dtype=getattr(torch, dtype) if isinstance(dtype, str) else dtype,
+                           device=f"cuda:{self.device}" if like is None else like.device)
+
+    def _like(self, src, *targets):
+        """src, an RGBA8 frame or batch of frames, checked; every target
+        checked, or allocated like src where it is None -> the targets."""
+        _check_out(src, src.numel())
+        return [self._out(t, src.shape, src.dtype, like=src) for t in targets]
+
+    def _call(self, fn, out, stats, *args, handle=None):
+        """fn(ctx (or handle), *args, an rm_stats or NULL), checked -> out, or
+        (out, the stats dict) with stats=True."""
+        if not stats:
+            check(fn(handle or self._ctx, *args, None), self._ctx)
+            return out
+        s = RmStats()
+        check(fn(handle or self._ctx, *args, ctypes.byref(s)), self._ctx)
+        return out, self._stats(s)
+
+    def _render(self, entry, rgba8, dims, out, stats, *args):
+        """One render entry point in its float form or, with rgba8, its RGBA8
+        form (entry + "_rgba8"), into `dims` pixels: entry(ctx, *args, out, stats)."""
+        if rgba8:
+            out, fn = self._out(out, dims), getattr(lib(), entry + "_rgba8")
+        else:
+            out, fn = self._out(out, dims + (4,), "float32"), getattr(lib(), entry)
+        return self._call(fn, out, stats, *args, self._ptr(out))
+
     def render(self, W: int, H: int, out=None, stats: bool = False):
         """Full frame into `out` (device tensor [H,W,4] f32; allocated if None)."""
-        torch = _torch()
-        if out is None:
-            out = torch.empty((H, W, 4), dtype=torch.float32, device=f"cuda:{self.device}")
-        _check_out(out, H * W * 4)
-        s = RmStats()
-        check(lib().rm_render(self._ctx, int(W), int(H), self._ptr(out), ctypes.byref(s) if stats else None),
-              self._ctx)
-        return (out, self._stats(s)) if stats else out
+        return self._render("rm_render", False, (H, W), out, stats, int(W), int(H))
 
     def render_accumulate(self, W: int, H: int, accum, stats: bool = False):
         """Progressive accumulation (rm_render_accumulate[_rgba8]): `accum` holds
@@ -237,23 +269,13 @@ class Renderer:
         rgba8 = accum.dtype == torch.int32
         if not rgba8 and accum.dtype != torch.float32:
             raise ValueError("render_accumulate: accum must be float32 [H, W, 4] or int32 RGBA8 words [H, W]")
-        _check_out(accum, H * W * (1 if rgba8 else 4))
-        s = RmStats()
-        fn = lib().rm_render_accumulate_rgba8 if rgba8 else lib().rm_render_accumulate
-        check(fn(self._ctx, int(W), int(H), self._ptr(accum), ctypes.byref(s) if stats else None), self._ctx)
-        return (accum, self._stats(s)) if stats else accum
+        return self._render("rm_render_accumulate", rgba8, (H, W), accum, stats, int(W), int(H))
 
     def render_step_map(self, W: int, H: int, out=None, evals_map=None):
         """Full frame plus the per-pixel sceneSDF call counts: (float32 [H, W, 4],
         int32 [H, W], stats), device tensors (allocated if None)."""
-        torch = _torch()
-        dev = f"cuda:{self.device}"
-        if out is None:
-            out = torch.empty((H, W, 4), dtype=torch.float32, device=dev)
-        if evals_map is None:
-            evals_map = torch.empty((H, W), dtype=torch.int32, device=dev)
-        _check_out(out, H * W * 4)
-        _check_out(evals_map, H * W)
+        out = self._out(out, (H, W, 4), "float32")
+        evals_map = self._out(evals_map, (H, W))
         s = RmStats()
         check(lib().rm_render_step_map(self._ctx, int(W), int(H), self._ptr(out), self._ptr(evals_map),
                                        ctypes.byref(s)), self._ctx)
@@ -261,39 +283,20 @@ class Renderer:
 
     def render_band(self, W: int, H: int, band: int, nshards: int, shard: int, out=None, stats: bool = False):
         """Rows y with (y // band) % nshards == shard, packed in increasing y."""
-        torch = _torch()
-        n = shard_rows(H, band, nshards, shard)
-        if out is None:
-            out = torch.empty((n, W, 4), dtype=torch.float32, device=f"cuda:{self.device}")
-        _check_out(out, n * W * 4)
-        s = RmStats()
-        check(lib().rm_render_band(self._ctx, int(W), int(H), int(band), int(nshards), int(shard), self._ptr(out),
-                                   ctypes.byref(s) if stats else None), self._ctx)
-        return (out, self._stats(s)) if stats else out
+        return self._render("rm_render_band", False, (shard_rows(H, band, nshards, shard), W), out, stats,
+                            int(W), int(H), int(band), int(nshards), int(shard))
 
     def render_rows(self, W, H, band, nshards, shard, row_begin, row_count, out, stats=False):
         """Packed rows [row_begin, row_begin + row_count) of a shard into `out`
         (float32 [rows, W, 4], or int32 [rows, W] RGBA8 words: the kernel packs)."""
-        torch = _torch()
-        rgba8 = out.dtype != torch.float32
-        _check_out(out, row_count * W * (1 if rgba8 else 4))
-        s = RmStats()
-        fn = lib().rm_render_rows_rgba8 if rgba8 else lib().rm_render_rows
-        check(fn(self._ctx, int(W), int(H), int(band), int(nshards), int(shard), int(row_begin), int(row_count),
-                 self._ptr(out), ctypes.byref(s) if stats else None), self._ctx)
-        return (out, self._stats(s)) if stats else out
+        return self._render("rm_render_rows", out.dtype != _torch().float32, (row_count, W), out, stats, int(W), int(H),
+                            int(band), int(nshards), int(shard), int(row_begin), int(row_count))
 
     def render_cycle_rows(self, W, H, cycle, offset, run, row_begin, row_count, out, stats=False):
         """Packed rows [row_begin, row_begin + row_count) of the cyclic part
         (y mod cycle) - offset in [0, run), as render_rows (float32 or RGBA8 out)."""
-        torch = _torch()
-        rgba8 = out.dtype != torch.float32
-        _check_out(out, row_count * W * (1 if rgba8 else 4))
-        s = RmStats()
-        fn = lib().rm_render_cycle_rows_rgba8 if rgba8 else lib().rm_render_cycle_rows
-        check(fn(self._ctx, int(W), int(H), int(cycle), int(offset), int(run), int(row_begin), int(row_count),
-                 self._ptr(out), ctypes.byref(s) if stats else None), self._ctx)
-        return (out, self._stats(s)) if stats else out
+        return self._render("rm_render_cycle_rows", out.dtype != _torch().float32, (row_count, W), out, stats, int(W),
+                            int(H), int(cycle), int(offset), int(run), int(row_begin), int(row_count))
 
     def deinterleave_cycle_rgb8(self, W, H, cycle, offsets, runs, part_bytes, gathered, out=None):
         """The RGBA8 frame (alpha 255) from cyclic parts' packed RGB8 rows:
@@ -308,9 +311,7 @@ class Renderer:
         for o, r, b in zip(offsets, runs, part_bytes):
             if b + cycle_rows(H, cycle, o, r) * 3 * W > gathered.numel():
                 raise ValueError("deinterleave_cycle_rgb8: a part's rows run past the end of gathered")
-        if out is None:
-            out = torch.empty((H, W), dtype=torch.int32, device=gathered.device)
-        _check_out(out, H * W)
+        out = self._out(out, (H, W), like=gathered)
         check(lib().rm_deinterleave_cycle_rgb8(self._ctx, int(W), int(H), int(cycle), n,
                                                (ctypes.c_int * n)(*offsets), (ctypes.c_int * n)(*runs),
                                                (ctypes.c_int64 * n)(*part_bytes), self._ptr(gathered),
@@ -324,19 +325,9 @@ class Renderer:
         `msg` uint8 of wire_capacity(W, row_count) bytes, `workspace` of
         wire_workspace_bytes(W, row_count), `size_out` an optional int64
         device tensor [1] for the message size (asynchronously)."""
-        torch = _torch()
-        if msg.dtype != torch.uint8 or msg.numel() < wire_capacity(W, row_count) or not msg.is_contiguous():
-            raise ValueError("render_cycle_rows_wire: msg must be a contiguous uint8 tensor of wire_capacity bytes")
-        if workspace.numel() * workspace.element_size() < wire_workspace_bytes(W, row_count):
-            raise ValueError("render_cycle_rows_wire: workspace too small")
-        if size_out is not None and (size_out.dtype != torch.int64 or size_out.numel() < 1):
-            raise ValueError("render_cycle_rows_wire: size_out must be an int64 tensor")
-        s = RmStats()
-        check(lib().rm_render_cycle_rows_wire(self._ctx, int(W), int(H), int(cycle), int(offset), int(run),
-                                              int(row_begin), int(row_count), self._ptr(msg), self._ptr(workspace),
-                                              self._ptr(size_out) if size_out is not None else None,
-                                              ctypes.byref(s) if stats else None), self._ctx)
-        return (msg, self._stats(s)) if stats else msg
+        _check_wire("render_cycle_rows_wire", W, row_count, msg, workspace, size_out)
+        return self._call(lib().rm_render_cycle_rows_wire, msg, stats, int(W), int(H), int(cycle), int(offset), int(run),
+                          int(row_begin), int(row_count), self._ptr(msg), self._ptr(workspace), self._ptr(size_out))
 
     def wire_encode(self, rows, msg, workspace, size_out=None):
         """Compressed wire of packed RGBA8 rows (int32 [n, W]) into the uint8
@@ -347,14 +338,9 @@ class Renderer:
         n, W = (int(rows.shape[0]), int(rows.shape[1])) if rows.dim() == 2 else (0, 0)
         if rows.dtype != torch.int32 or not rows.is_contiguous() or rows.dim() != 2:
             raise ValueError("wire_encode: rows must be contiguous int32 [n, W] RGBA8 words")
-        if msg.dtype != torch.uint8 or msg.numel() < wire_capacity(W, n) or not msg.is_contiguous():
-            raise ValueError("wire_encode: msg must be a contiguous uint8 tensor of wire_capacity bytes")
-        if workspace.numel() * workspace.element_size() < wire_workspace_bytes(W, n):
-            raise ValueError("wire_encode: workspace too small")
-        if size_out is not None and (size_out.dtype != torch.int64 or size_out.numel() < 1):
-            raise ValueError("wire_encode: size_out must be an int64 tensor")
+        _check_wire("wire_encode", W, n, msg, workspace, size_out)
         check(lib().rm_wire_encode(self._ctx, W, n, self._ptr(rows), self._ptr(msg), self._ptr(workspace),
-                                   self._ptr(size_out) if size_out is not None else None), self._ctx)
+                                   self._ptr(size_out)), self._ctx)
         return msg
 
     def wire_decode(self, W, H, cycle, offset, run, nrows, msg, frame):
@@ -386,37 +372,23 @@ class Renderer:
 
     def render_band_rgba8(self, W, H, band, nshards, shard, out=None, stats=False):
         """render_band into RGBA8 words ([rows, W] int32)."""
-        torch = _torch()
-        n = shard_rows(H, band, nshards, shard)
-        if out is None:
-            out = torch.empty((n, W), dtype=torch.int32, device=f"cuda:{self.device}")
-        _check_out(out, n * W)
-        s = RmStats()
-        check(lib().rm_render_band_rgba8(self._ctx, int(W), int(H), int(band), int(nshards), int(shard),
-                                         self._ptr(out), ctypes.byref(s) if stats else None), self._ctx)
-        return (out, self._stats(s)) if stats else out
+        return self._render("rm_render_band", True, (shard_rows(H, band, nshards, shard), W), out, stats,
+                            int(W), int(H), int(band), int(nshards), int(shard))
 
     def deinterleave(self, W, H, band, nshards, rows_per_shard, gathered, out=None):
         """gathered: [nshards, rows_per_shard, W, 4] f32, [nshards, rows_per_shard, W] RGBA8 words, or
         [nshards, rows_per_shard, 3 * W] uint8 (the RGB8 wire; the frame is RGBA8 words, alpha 255)."""
         torch = _torch()
-        if gathered.dtype == torch.uint8:
-            if out is None:
-                out = torch.empty((H, W), dtype=torch.int32, device=gathered.device)
-            _check_out(out, H * W)
+        wire = gathered.dtype == torch.uint8
+        rgba8 = gathered.dtype != torch.float32  # RGBA8 words travel as int32
+        out = self._out(out, (H, W) if rgba8 else (H, W, 4), "int32" if wire else gathered.dtype, like=gathered)
+        if wire:
             if gathered.numel() < nshards * rows_per_shard * W * 3 or not gathered.is_contiguous():
                 raise ValueError("deinterleave: RGB8 wire must be contiguous with 3*W bytes per row")
-            check(lib().rm_deinterleave_rgb8(self._ctx, W, H, band, nshards, rows_per_shard, self._ptr(gathered),
-                                             self._ptr(out)), self._ctx)
-            return out
-        rgba8 = gathered.dtype != torch.float32  # RGBA8 words travel as int32
-        per_px = 1 if rgba8 else 4
-        if out is None:
-            shape = (H, W) if rgba8 else (H, W, 4)
-            out = torch.empty(shape, dtype=gathered.dtype, device=gathered.device)
-        _check_out(out, H * W * per_px)
-        _check_out(gathered, nshards * rows_per_shard * W * per_px)
-        fn = lib().rm_deinterleave_rgba8 if rgba8 else lib().rm_deinterleave
+            fn = lib().rm_deinterleave_rgb8
+        else:
+            _check_out(gathered, nshards * rows_per_shard * W * (1 if rgba8 else 4))
+            fn = lib().rm_deinterleave_rgba8 if rgba8 else lib().rm_deinterleave
         check(fn(self._ctx, W, H, band, nshards, rows_per_shard, self._ptr(gathered), self._ptr(out)), self._ctx)
         return out
 
@@ -447,23 +419,15 @@ class Renderer:
 
     def fxaa(self, frame8, out=None):
         """post.frag's FXAA over an [H, W] RGBA8 (int32 words) device frame."""
-        torch = _torch()
         H, W = frame8.shape
-        if out is None:
-            out = torch.empty_like(frame8)
-        _check_out(frame8, H * W)
-        _check_out(out, H * W)
+        (out,) = self._like(frame8, out)
         check(lib().rm_fxaa(self._ctx, W, H, self._ptr(frame8), self._ptr(out)), self._ctx)
         return out
 
     def bloom(self, frame8, out=None):
         """bloom.frag (with its mip chain) over an [H, W] RGBA8 (int32 words) device frame."""
-        torch = _torch()
         H, W = frame8.shape
-        if out is None:
-            out = torch.empty_like(frame8)
-        _check_out(frame8, H * W)
-        _check_out(out, H * W)
+        (out,) = self._like(frame8, out)
         check(lib().rm_bloom(self._ctx, W, H, self._ptr(frame8), self._ptr(out)), self._ctx)
         return out
 
@@ -471,25 +435,16 @@ class Renderer:
     def _post_choice(sample, tonemap):
         """(sample, tonemap) names or rm.h values -> values; an int passes
         through for the library to judge."""
-        def value(v, table, what):
-            if isinstance(v, str):
-                if v not in table:
-                    raise ValueError(f"{what} must be one of {sorted(table)}, not {v!r}")
-                return table[v]
-            return int(v)
-        return value(sample, _lib.POST_SAMPLES, "sample"), value(tonemap, _lib.TONEMAPS, "tonemap")
+        return (int(_lib.named(sample, _lib.POST_SAMPLES, "sample")),
+                int(_lib.named(tonemap, _lib.TONEMAPS, "tonemap")))
 
     def post_frag(self, frame8, sample="fxaa", tonemap="none", out=None):
         """post.frag's main() over an [H, W] RGBA8 (int32 words) device frame
         with its sample ("fxaa", "texel", "chromatic": POST_SAMPLES) and tonemap
         operator (TONEMAPS) chosen (rm_post_frag); the defaults are fxaa()."""
-        torch = _torch()
         s, t = self._post_choice(sample, tonemap)
         H, W = frame8.shape
-        if out is None:
-            out = torch.empty_like(frame8)
-        _check_out(frame8, H * W)
-        _check_out(out, H * W)
+        (out,) = self._like(frame8, out)
         check(lib().rm_post_frag(self._ctx, W, H, s, t, self._ptr(frame8), self._ptr(out)), self._ctx)
         return out
 
@@ -498,14 +453,8 @@ class Renderer:
         then bloom of mid into out (rm_post_chain); returns (mid, out).  With a
         sample or tonemap other than the defaults the first pass is post_frag's
         (rm_post_chain_ex)."""
-        torch = _torch()
         H, W = frame8.shape
-        if mid is None:
-            mid = torch.empty_like(frame8)
-        if out is None:
-            out = torch.empty_like(frame8)
-        for t in (frame8, mid, out):
-            _check_out(t, H * W)
+        mid, out = self._like(frame8, mid, out)
         if (sample, tonemap) == ("fxaa", "none"):
             check(lib().rm_post_chain(self._ctx, W, H, self._ptr(frame8), self._ptr(mid), self._ptr(out)), self._ctx)
         else:
@@ -515,21 +464,13 @@ class Renderer:
         return mid, out
 
     # --- the post passes over a batch of frames (rm_post_chain_batch) ---
-    def _post_batch_bufs(self, frames8, *others):
-        """frames8 [n, H, W] and the targets (allocated like it where None) -> n, H, W, targets."""
-        torch = _torch()
-        n, H, W = frames8.shape
-        bufs = [torch.empty_like(frames8) if t is None else t for t in others]
-        for t in (frames8, *bufs):
-            _check_out(t, n * H * W)
-        return n, H, W, bufs
-
     def post_frag_batch(self, frames8, sample="fxaa", tonemap="none", out=None):
         """post_frag of every frame of an [n, H, W] RGBA8 (int32 words) device
         batch in one launch (rm_post_frag_batch): out[v] is byte for byte
         post_frag(frames8[v]) with the same sample and tonemap."""
         s, t = self._post_choice(sample, tonemap)
-        n, H, W, (out,) = self._post_batch_bufs(frames8, out)
+        n, H, W = frames8.shape
+        (out,) = self._like(frames8, out)
         check(lib().rm_post_frag_batch(self._ctx, W, H, n, s, t, self._ptr(frames8), self._ptr(out)), self._ctx)
         return out
 
@@ -538,7 +479,8 @@ class Renderer:
         (rm_bloom_batch): out[v] is byte for byte bloom(frames8[v]).  The
         launches do not grow with n, but for the groups the scratch limit
         makes (post_batch_plan, set_post_batch_scratch_limit)."""
-        n, H, W, (out,) = self._post_batch_bufs(frames8, out)
+        n, H, W = frames8.shape
+        (out,) = self._like(frames8, out)
         check(lib().rm_bloom_batch(self._ctx, W, H, n, self._ptr(frames8), self._ptr(out)), self._ctx)
         return out
 
@@ -548,7 +490,8 @@ class Renderer:
         (mid, out), whose view v is byte for byte post_chain(frames8[v]) with
         the same sample and tonemap.  frames8, mid and out must not overlap."""
         s, t = self._post_choice(sample, tonemap)
-        n, H, W, (mid, out) = self._post_batch_bufs(frames8, mid, out)
+        n, H, W = frames8.shape
+        mid, out = self._like(frames8, mid, out)
         check(lib().rm_post_chain_batch(self._ctx, W, H, n, s, t, self._ptr(frames8), self._ptr(mid),
                                         self._ptr(out)), self._ctx)
         return mid, out
@@ -560,7 +503,7 @@ class Renderer:
         runs in groups (post_batch_plan)."""
         check(lib().rm_set_post_batch_scratch_limit(self._ctx, int(nbytes)), self._ctx)
 
-    SCENE_FORMS ={"exact": 0, "probe": 1, "probe_nb1": 2}  # rm.h rm_form
+    SCENE_FORMS = _lib.SCENE_FORMS  # rm.h rm_form
 
     def scene_eval(self, points, material: bool = False, form: str = "exact", aux: bool = False):
         """sceneSDF(p) of the loaded scene at points [n, 3] (host, numpy):
@@ -580,10 +523,10 @@ class Renderer:
         ax = np.zeros(n, np.float32) if aux else None
         if form == "exact" and not aux:
             check(lib().rm_scene_eval(self._ctx, self._ptr(pts), n, self._ptr(dist),
-                                      self._ptr(mat) if material else None), self._ctx)
+                                      self._ptr(mat)), self._ctx)
         else:
             check(lib().rm_scene_eval_form(self._ctx, self._ptr(pts), n, self.SCENE_FORMS[form], self._ptr(dist),
-                                           self._ptr(mat) if material else None, self._ptr(ax) if aux else None),
+                                           self._ptr(mat), self._ptr(ax)),
                   self._ctx)
         out = (dist,) + ((mat,) if material else ()) + ((ax,) if aux else ())
         return out if len(out) > 1 else dist
@@ -599,27 +542,17 @@ class Renderer:
         status [n] i32 (RM_RAY_*), steps [n] i32, position [n, 3][, normal
         [n, 3]][, material [n, 16]][, stats])."""
         import numpy as np
-        on_device = hasattr(directions, "data_ptr") and directions.is_cuda
+        o, d, n, shared, on_device = _ray_inputs("cast_rays", origins, directions, shared_on_host=False)
         if on_device:
             torch = _torch()
-            dev = directions.device
-            d = directions.to(torch.float32).reshape(-1, 3).contiguous()
-            o = torch.as_tensor(origins, dtype=torch.float32, device=dev).contiguous()
 
             def empty(shape, dtype=torch.float32):
-                return torch.empty(shape, dtype=dtype, device=dev)
+                return torch.empty(shape, dtype=dtype, device=d.device)
             i32 = torch.int32
         else:
-            d = np.ascontiguousarray(np.asarray(directions), np.float32).reshape(-1, 3)
-            o = np.ascontiguousarray(np.asarray(origins), np.float32)
-
             def empty(shape, dtype=np.float32):
                 return np.empty(shape, dtype)
             i32 = np.int32
-        n = len(d)
-        shared = o.ndim == 1
-        if tuple(o.shape) != ((3,) if shared else (n, 3)):
-            raise ValueError(f"cast_rays: origins {tuple(o.shape)} for {n} directions; expected [3] or [{n}, 3]")
         out = dict(t=empty(n), status=empty(n, i32), steps=empty(n, i32), position=empty((n, 3)))
         if normal:
             out["normal"] = empty((n, 3))
@@ -627,11 +560,10 @@ class Renderer:
             out["material"] = empty((n, 16))
         hits = _lib.RmRayHits(*(self._ptr(out[k]) if k in out and n else None
                                 for k in ("t", "status", "steps", "position", "normal", "material")))
-        s = RmStats()
-        check(lib().rm_cast_rays(self._ctx, self._ptr(o), int(shared), self._ptr(d), n, int(bool(inside)),
-                                 ctypes.byref(hits), ctypes.byref(s) if stats else None), self._ctx)
+        res = self._call(lib().rm_cast_rays, out, stats, self._ptr(o), int(shared), self._ptr(d), n,
+                         int(bool(inside)), ctypes.byref(hits))
         if stats:
-            out["stats"] = self._stats(s)
+            out["stats"] = res[1]
         return out
 
     def camera_rays(self, W: int, H: int):
@@ -664,50 +596,18 @@ class Renderer:
         import numpy as np
         if output not in _lib.SHADE_OUTPUTS:
             raise ValueError(f"shade_rays: output {output!r}; expected one of {sorted(_lib.SHADE_OUTPUTS)}")
-        on_device = hasattr(directions, "data_ptr") and directions.is_cuda
-        if on_device:
-            torch = _torch()
-            d = directions.to(torch.float32).reshape(-1, 3)
-            if normalize:
-                d = d / torch.linalg.vector_norm(d, dim=1, keepdim=True)
-            d = d.contiguous()
-            o = torch.as_tensor(origins, dtype=torch.float32)
-            # (the shared origin is read on the host; origins per ray live where the directions do)
-            o = (o.cpu() if o.ndim == 1 else o.to(d.device)).contiguous()
-        else:
-            d = np.ascontiguousarray(np.asarray(directions), np.float32).reshape(-1, 3)
-            if normalize:
-                d = d / np.sqrt((d * d).sum(1, dtype=np.float32, keepdims=True), dtype=np.float32)
-            if hasattr(origins, "data_ptr"):
-                origins = origins.cpu().numpy()
-            o = np.ascontiguousarray(np.asarray(origins), np.float32)
-        n = len(d)
-        shared = o.ndim == 1
-        if tuple(o.shape) != ((3,) if shared else (n, 3)):
-            raise ValueError(f"shade_rays: origins {tuple(o.shape)} for {n} directions; expected [3] or [{n}, 3]")
-        if out is None:
-            if on_device:
-                out = torch.empty((n,) if rgba8 else (n, 4), dtype=torch.int32 if rgba8 else torch.float32,
-                                  device=d.device)
-            else:
-                out = np.empty((n,) if rgba8 else (n, 4), np.uint32 if rgba8 else np.float32)
-        _check_out(out, n if rgba8 else 4 * n)
+        # the shared origin is read on the host (cast_rays reads it where the directions live)
+        o, d, n, shared, on_device = _ray_inputs("shade_rays", origins, directions, shared_on_host=True,
+                                                 normalize=normalize)
+        if out is None and not on_device:
+            out = np.empty((n,) if rgba8 else (n, 4), np.uint32 if rgba8 else np.float32)
+        out = self._out(out, (n,), like=d) if rgba8 else self._out(out, (n, 4), "float32", like=d)
         p = _lib.RmShadeParams(int(width), _lib.SHADE_OUTPUTS[output], int(bool(vignette)))
-        s = RmStats()
-        check(lib().rm_shade_rays(self._ctx, self._ptr(o), int(shared), self._ptr(d), n, ctypes.byref(p),
-                                  None if rgba8 else self._ptr(out), self._ptr(out) if rgba8 else None,
-                                  ctypes.byref(s) if stats else None), self._ctx)
-        return (out, self._stats(s)) if stats else out
+        return self._call(lib().rm_shade_rays, out, stats, self._ptr(o), int(shared), self._ptr(d), n, ctypes.byref(p),
+                          None if rgba8 else self._ptr(out), self._ptr(out) if rgba8 else None)
 
     def render_rgba8(self, W, H, out=None, stats=False):
-        torch = _torch()
-        if out is None:
-            out = torch.empty((H, W), dtype=torch.int32, device=f"cuda:{self.device}")
-        _check_out(out, H * W)
-        s = RmStats()
-        check(lib().rm_render_rgba8(self._ctx, W, H, self._ptr(out), ctypes.byref(s) if stats else None),
-              self._ctx)
-        return (out, self._stats(s)) if stats else out
+        return self._render("rm_render", True, (H, W), out, stats, W, H)
 
     # --- view batches (rm_render_batch, rm_render_batch_rgba8) -------------
     def render_batch(self, W: int, H: int, views, out=None, rgba8: bool = True, stats: bool = False):
@@ -726,18 +626,7 @@ class Renderer:
         timed kernels in row-major one-wave tiles, always: kernel, schedule,
         count_evals and set_tile_order do not apply.  Built-in scenes only."""
         v = pack_views(views)
-        n = len(v)
-        per_px = 1 if rgba8 else 4
-        if out is None:
-            torch = _torch()
-            out = torch.empty((n, H, W) if rgba8 else (n, H, W, 4), dtype=torch.int32 if rgba8 else torch.float32,
-                              device=f"cuda:{self.device}")
-        _check_out(out, n * H * W * per_px)
-        s = RmStats()
-        fn = lib().rm_render_batch_rgba8 if rgba8 else lib().rm_render_batch
-        check(fn(self._ctx, int(W), int(H), ctypes.c_void_p(v.ctypes.data), n, self._ptr(out),
-                 ctypes.byref(s) if stats else None), self._ctx)
-        return (out, self._stats(s)) if stats else out
+        return self._render("rm_render_batch", rgba8, (len(v), H, W), out, stats, int(W), int(H), self._ptr(v), len(v))
 
     def render_batch_ex(self, W: int, H: int, views, uniforms=None, out=None, rgba8: bool = True,
                         stats: bool = False):
@@ -779,18 +668,8 @@ class Renderer:
             entries.append(_lib.RmViewUniform(keep[-1][0], int(a.shape[2]), int(a.shape[1]),
                                               ctypes.c_void_p(a.ctypes.data)))
         arr = (_lib.RmViewUniform * max(1, len(entries)))(*entries)
-        per_px = 1 if rgba8 else 4
-        if out is None:
-            torch = _torch()
-            out = torch.empty((n, H, W) if rgba8 else (n, H, W, 4), dtype=torch.int32 if rgba8 else torch.float32,
-                              device=f"cuda:{self.device}")
-        _check_out(out, n * H * W * per_px)
-        s = RmStats()
-        fn = lib().rm_render_batch_ex_rgba8 if rgba8 else lib().rm_render_batch_ex
-        check(fn(self._ctx, int(W), int(H), ctypes.c_void_p(v.ctypes.data), n,
-                 ctypes.cast(arr, ctypes.c_void_p) if entries else None, len(entries), self._ptr(out),
-                 ctypes.byref(s) if stats else None), self._ctx)
-        return (out, self._stats(s)) if stats else out
+        return self._render("rm_render_batch_ex", rgba8, (n, H, W), out, stats, int(W), int(H), self._ptr(v), n,
+                            ctypes.cast(arr, ctypes.c_void_p) if entries else None, len(entries))
 
     def batch_prepare(self) -> None:
         """rm_batch_prepare: compile and load the loaded plugin's batch kernel
@@ -811,7 +690,7 @@ class Renderer:
                  else np.empty((H, W), np.uint8))
         p = _lib.RmAaParams(int(samples), int(threshold))
         s = _lib.RmAaStats()
-        check(fn(self._ctx, int(W), int(H), ctypes.byref(p), self._ptr(frame8), self._ptr(m) if mask else None,
+        check(fn(self._ctx, int(W), int(H), ctypes.byref(p), self._ptr(frame8), self._ptr(m),
                  ctypes.byref(s) if stats else None), self._ctx)
         res = (frame8,) + ((m,) if mask else ()) + ((s.as_dict(),) if stats else ())
         return res if len(res) > 1 else frame8
@@ -827,9 +706,7 @@ class Renderer:
         array.  Returns out, then with mask=True the uint8 [H, W] mask of the
         refined pixels, then with stats=True dict(refined, base_ms, detect_ms,
         refine_ms) (which waits for the frame).  Built-in scenes only."""
-        if out is None:
-            out = _torch().empty((H, W), dtype=_torch().int32, device=f"cuda:{self.device}")
-        return self._aa(lib().rm_render_aa_rgba8, W, H, samples, threshold, out, mask, stats)
+        return self._aa(lib().rm_render_aa_rgba8, W, H, samples, threshold, self._out(out, (H, W)), mask, stats)
 
     def refine(self, frame8, samples=4, threshold=32, mask=False, stats=False):
         """rm_refine_rgba8: the supersampling step of render_aa on any [H, W]
@@ -847,9 +724,7 @@ class Renderer:
         is compiled on the first call after load_scene (aa_prepare compiles it
         ahead).  For a built-in scene: render_aa.  Arguments and results as
         render_aa's."""
-        if out is None:
-            out = _torch().empty((H, W), dtype=_torch().int32, device=f"cuda:{self.device}")
-        return self._aa(lib().rm_render_aa_ex_rgba8, W, H, samples, threshold, out, mask, stats)
+        return self._aa(lib().rm_render_aa_ex_rgba8, W, H, samples, threshold, self._out(out, (H, W)), mask, stats)
 
     def refine_ex(self, frame8, samples=4, threshold=32, mask=False, stats=False):
         """rm_refine_ex_rgba8: refine for any scene, a scene plugin included;
@@ -865,12 +740,11 @@ class Renderer:
         check(lib().rm_aa_prepare(self._ctx), self._ctx)
 
     # --- adaptive supersampling of a view batch (rm_render_batch_aa_rgba8, rm_refine_batch_rgba8) ---
-    def _batch_aa(self, fn, W, H, views, samples, threshold, frames8, mask, refined, stats):
-        """frames8: [n, H, W] RGBA8 words, a device tensor or a numpy array
-        (staged); the mask and the per-view counts live where the frames do.
-        -> frames8[, mask][, refined][, stats]."""
+    def _batch_aa(self, fn, W, H, v, samples, threshold, frames8, mask, refined, stats):
+        """v: the packed views.  frames8: [n, H, W] RGBA8 words, a device tensor
+        or a numpy array (staged); the mask and the per-view counts live where
+        the frames do.  -> frames8[, mask][, refined][, stats]."""
         import numpy as np
-        v = pack_views(views)
         n = len(v)
         on_device = hasattr(frames8, "data_ptr")
         _check_out(frames8, n * H * W)
@@ -884,7 +758,7 @@ class Renderer:
         p = _lib.RmAaParams(int(samples), int(threshold))
         s = _lib.RmAaStats()
         check(fn(self._ctx, int(W), int(H), ctypes.c_void_p(v.ctypes.data), n, ctypes.byref(p), self._ptr(frames8),
-                 self._ptr(m) if mask else None, self._ptr(r) if refined else None,
+                 self._ptr(m), self._ptr(r),
                  ctypes.byref(s) if stats else None), self._ctx)
         res = (frames8,) + ((m,) if mask else ()) + ((r,) if refined else ()) + ((s.as_dict(),) if stats else ())
         return res if len(res) > 1 else frames8
@@ -903,20 +777,19 @@ class Renderer:
         device, uint32 in numpy), then with stats=True dict(refined, base_ms,
         detect_ms, refine_ms) -- refined summed over the views, detect_ms with
         the plan step (which waits for the frames).  Built-in scenes only."""
-        if out is None:
-            out = _torch().empty((len(pack_views(views)), H, W), dtype=_torch().int32, device=f"cuda:{self.device}")
-        return self._batch_aa(lib().rm_render_batch_aa_rgba8, W, H, views, samples, threshold, out, mask, refined,
-                              stats)
+        v = pack_views(views)
+        return self._batch_aa(lib().rm_render_batch_aa_rgba8, W, H, v, samples, threshold,
+                              self._out(out, (len(v), H, W)), mask, refined, stats)
 
     def refine_batch(self, frames8, views, samples=4, threshold=32, mask=False, refined=False, stats=False):
         """rm_refine_batch_rgba8: the supersampling step of render_batch_aa on
         any [n, H, W] RGBA8 frames of the views (normally render_batch's), in
         place; returns as render_batch_aa does."""
         n, H, W = frames8.shape
-        if n != len(pack_views(views)):
-            raise ValueError(f"refine_batch: {n} frames for {len(pack_views(views))} views")
-        return self._batch_aa(lib().rm_refine_batch_rgba8, W, H, views, samples, threshold, frames8, mask, refined,
-                              stats)
+        v = pack_views(views)
+        if n != len(v):
+            raise ValueError(f"refine_batch: {n} frames for {len(v)} views")
+        return self._batch_aa(lib().rm_refine_batch_rgba8, W, H, v, samples, threshold, frames8, mask, refined, stats)
 
 
 def batch_aa_scratch_bytes(W: int, H: int, n: int) -> int:
@@ -1004,8 +877,7 @@ def sharded_layout(W: int, H: int, band: int, nranks: int, rank: int) -> dict:
     """rm_sharded_layout: the row/byte layout of rm_render_sharded (no GPU)."""
     L = _lib.RmShardLayout()
     check(lib().rm_sharded_layout(int(W), int(H), int(band), int(nranks), int(rank), ctypes.byref(L)))
-    return dict(rows_mine=L.rows_mine, rows_per_shard=L.rows_per_shard, wire_bytes=L.wire_bytes,
-                gathered_bytes=L.gathered_bytes)
+    return L.as_dict()
 
 
 def comm_get_id() -> bytes:
@@ -1048,32 +920,22 @@ class Comm:
         """One sharded frame (collective over the ranks).  Rank 0 gets the
         [H, W] RGBA8 (int32 words) frame, the others None.  runs: weighted
         parts (rm_render_sharded_runs, one run per rank) instead of bands."""
-        torch = _torch()
-        if self.rank == 0 and frame is None:
-            frame = torch.empty((H, W), dtype=torch.int32, device=f"cuda:{self.r.device}")
-        if frame is not None:
-            _check_out(frame, H * W)
-        s = RmStats()
-        fp = self.r._ptr(frame) if frame is not None else None
-        sp = ctypes.byref(s) if stats else None
+        if self.rank == 0 or frame is not None:
+            frame = self.r._out(frame, (H, W))
         if runs is not None:
             if len(runs) != self.nranks:
                 raise ValueError(f"runs needs {self.nranks} entries")
-            check(lib().rm_render_sharded_runs(self._h, int(W), int(H), (ctypes.c_int * len(runs))(*runs), fp, sp),
-                  self.r._ctx)
+            fn, part = lib().rm_render_sharded_runs, (ctypes.c_int * len(runs))(*runs)
         else:
-            check(lib().rm_render_sharded(self._h, int(W), int(H), int(band), fp, sp), self.r._ctx)
-        return (frame, self.r._stats(s)) if stats else frame
+            fn, part = lib().rm_render_sharded, int(band)
+        return self.r._call(fn, frame, stats, int(W), int(H), part, self.r._ptr(frame), handle=self._h)
 
     @staticmethod
     def render_all(comms, W: int, H: int, band: int = 16, frame=None, stats: bool = False, runs=None):
         """rm_render_sharded_all (or, with runs, rm_render_sharded_runs_all)
         over the communicators of init_all."""
-        torch = _torch()
         n = len(comms)
-        if frame is None:
-            frame = torch.empty((H, W), dtype=torch.int32, device=f"cuda:{comms[0].r.device}")
-        _check_out(frame, H * W)
+        frame = comms[0].r._out(frame, (H, W))
         hs = (ctypes.c_void_p * n)(*[c._h.value for c in comms])
         st = (RmStats * n)()
         if runs is not None:
@@ -1104,50 +966,84 @@ class Comm:
             pass
 
 
-def compile_scene(file_name: str):
-    """rm_compile_scene: compile a scene plugin with hiprtc, no GPU needed.
-    Returns (ok, log); a missing file or #include raises RmError."""
+def _compile(fn, file_name):
     buf = ctypes.create_string_buffer(1 << 16)
-    st = lib().rm_compile_scene(file_name.encode(), ctypes.cast(buf, ctypes.c_void_p), len(buf))
+    st = fn(file_name.encode(), ctypes.cast(buf, ctypes.c_void_p), len(buf))
     log = buf.value.decode(errors="replace")
     if st == _lib.STATUS_CODES["RM_ERR_FILE"]:
         raise _lib.RmError(st, log)
     return st == 0, log
+
+
+def compile_scene(file_name: str):
+    """rm_compile_scene: compile a scene plugin with hiprtc, no GPU needed.
+    Returns (ok, log); a missing file or #include raises RmError."""
+    return _compile(lib().rm_compile_scene, file_name)
 
 
 def compile_scene_batch(file_name: str):
     """rm_compile_scene_batch: compile_scene for the batch form of a plugin's
     code object (Renderer.render_batch_ex's kernel).  (False, log) for a scene
     that defines RM_PLUGIN_EVAL_ONLY."""
-    buf = ctypes.create_string_buffer(1 << 16)
-    st = lib().rm_compile_scene_batch(file_name.encode(), ctypes.cast(buf, ctypes.c_void_p), len(buf))
-    log = buf.value.decode(errors="replace")
-    if st == _lib.STATUS_CODES["RM_ERR_FILE"]:
-        raise _lib.RmError(st, log)
-    return st == 0, log
+    return _compile(lib().rm_compile_scene_batch, file_name)
 
 
 def compile_scene_aa(file_name: str):
     """rm_compile_scene_aa: compile_scene for the AA form of a plugin's code
     object (Renderer.render_aa_ex's refine kernel).  (False, log) for a scene
     that defines RM_PLUGIN_EVAL_ONLY."""
-    buf = ctypes.create_string_buffer(1 << 16)
-    st = lib().rm_compile_scene_aa(file_name.encode(), ctypes.cast(buf, ctypes.c_void_p), len(buf))
-    log = buf.value.decode(errors="replace")
-    if st == _lib.STATUS_CODES["RM_ERR_FILE"]:
-        raise _lib.RmError(st, log)
-    return st == 0, log
+    return _compile(lib().rm_compile_scene_aa, file_name)
 
 
-def _check_out(t, nfloats):
+def _check_out(t, n):
     """A buffer the C ABI reads or writes as 32-bit words: a contiguous torch
-    tensor or numpy array of 4-byte elements with at least `nfloats` of them."""
+    tensor or numpy array of 4-byte elements with at least `n` of them."""
     if hasattr(t, "is_contiguous"):
-        ok, n, es = t.is_contiguous(), t.numel(), t.element_size()
+        ok, have, es = t.is_contiguous(), t.numel(), t.element_size()
     else:
-        ok, n, es = bool(t.flags["C_CONTIGUOUS"]), t.size, t.itemsize
-    if not ok or n < nfloats or es != 4:
-        raise ValueError(f"buffer must be contiguous 32-bit with >= {nfloats} elements")
+        ok, have, es = bool(t.flags["C_CONTIGUOUS"]), t.size, t.itemsize
+    if not ok or have < n or es != 4:
+        raise ValueError(f"buffer must be contiguous 32-bit with >= {n} elements")
+
+
+def _check_wire(what, W, nrows, msg, workspace, size_out):
+    """The buffers of a wire message of nrows rows of W pixels."""
+    torch = _torch()
+    if msg.dtype != torch.uint8 or msg.numel() < wire_capacity(W, nrows) or not msg.is_contiguous():
+        raise ValueError(f"{what}: msg must be a contiguous uint8 tensor of wire_capacity bytes")
+    if workspace.numel() * workspace.element_size() < wire_workspace_bytes(W, nrows):
+        raise ValueError(f"{what}: workspace too small")
+    if size_out is not None and (size_out.dtype != torch.int64 or size_out.numel() < 1):
+        raise ValueError(f"{what}: size_out must be an int64 tensor")
+
+
+def _ray_inputs(what, origins, directions, shared_on_host, normalize=False):
+    """The rays of cast_rays / shade_rays -> (origins, directions, n, shared,
+    on_device): float32, directions contiguous [n, 3] (normalised in f32 with
+    normalize), origins [3] (shared by all rays) or [n, 3].  numpy arrays, or,
+    where directions is a CUDA tensor, torch tensors on its device -- but for a
+    shared origin with shared_on_host, which then stays on the host."""
+    import numpy as np
+    on_device = hasattr(directions, "data_ptr") and directions.is_cuda
+    if on_device:
+        torch = _torch()
+        d = directions.to(torch.float32).reshape(-1, 3)
+        if normalize:
+            d = d / torch.linalg.vector_norm(d, dim=1, keepdim=True)
+        d = d.contiguous()
+        o = torch.as_tensor(origins, dtype=torch.float32)
+        o = (o.cpu() if o.ndim == 1 and shared_on_host else o.to(d.device)).contiguous()
+    else:
+        d = np.ascontiguousarray(np.asarray(directions), np.float32).reshape(-1, 3)
+        if normalize:
+            d = d / np.sqrt((d * d).sum(1, dtype=np.float32, keepdims=True), dtype=np.float32)
+        if hasattr(origins, "data_ptr"):
+            origins = origins.cpu().numpy()
+        o = np.ascontiguousarray(np.asarray(origins), np.float32)
+    n, shared = len(d), o.ndim == 1
+    if tuple(o.shape) != ((3,) if shared else (n, 3)):
+        raise ValueError(f"{what}: origins {tuple(o.shape)} for {n} directions; expected [3] or [{n}, 3]")
+    return o, d, n, shared, on_device
 
 
 def render_code_hash() -> str:
