@@ -24,6 +24,7 @@ import oracle
 import raymarching_amd as rm
 from raymarching_amd import POSES
 from tests import aa_ref
+from tests import sentinel
 from tests.parity import FULL_SIZE_STEP_MAP, assert_parity
 
 pytestmark = pytest.mark.gpu
@@ -68,7 +69,8 @@ def setup(r, pose, steps, count_evals, kernel="auto", schedule=0):
 
 @pytest.mark.parametrize("kernel", ["tile8", "tile16", "persist"])
 @pytest.mark.parametrize("pose_name", list(POSE_SET))
-def test_timed_frame_equals_instrumented_frame(R, pose_name, kernel):
+def test_timed_frame_equals_instrumented_frame(R, torch_cuda, pose_name, kernel):
+    torch = torch_cuda
     pose = POSE_SET[pose_name]
     for W, H in SIZES:
         for steps in STEPS:
@@ -85,11 +87,15 @@ def test_timed_frame_equals_instrumented_frame(R, pose_name, kernel):
             assert np.array_equal(bits(f), ref4), f"{what}: timed float4 (row-major) differs"
             assert np.array_equal(bits(R.render_rgba8(W, H)), ref8), f"{what}: timed RGBA8 (row-major) differs"
             R.set_params(schedule=1)
+            # (every launch into a target no launch has written, tests/sentinel.py: a tile the order never
+            # dispatched shows instead of keeping the previous launch's pixels)
             for i in range(2):  # (the second launch of a geometry has an order and, in scene T, latency tiles)
-                o8, st8 = R.render_rgba8(W, H, stats=True)
+                o8, st8 = R.render_rgba8(W, H, out=sentinel.target(torch, (H, W), torch.int32), stats=True)
+                sentinel.assert_frame(o8, ref8, f"{what}: timed RGBA8 (schedule 1, launch {i})")
                 assert np.array_equal(bits(o8), ref8), f"{what}: timed RGBA8 (schedule 1, launch {i}) differs"
             for i in range(2):
-                f, st4 = R.render(W, H, stats=True)
+                f, st4 = R.render(W, H, out=sentinel.target(torch, (H, W, 4), torch.float32), stats=True)
+                sentinel.assert_frame(f, ref4, f"{what}: timed float4 (schedule 1, launch {i})")
                 assert np.array_equal(bits(f), ref4), f"{what}: timed float4 (schedule 1, launch {i}) differs"
             if kernel != "tile16":  # (the four-wave workgroups have no tile order)
                 assert st8["dispatch"] == "adaptive" and st8["lat_tiles"] > 0, st8

@@ -10,6 +10,7 @@ import pytest
 import oracle
 import raymarching_amd as rm
 from raymarching_amd import POSES, S0_POSE
+from tests import sentinel
 from tests.parity import FULL_SIZE_POLICY, FULL_SIZE_STEP_MAP, assert_parity, diff_stats
 
 pytestmark = pytest.mark.gpu
@@ -814,20 +815,40 @@ def test_adaptive_dispatch_order_keeps_pixels(R, torch_cuda, scene):
     ref_f = R.render(W, H)
     ref8 = R.render_rgba8(W, H)
     R.set_params(schedule=1)
+    # every ordered launch writes into a target that holds a word no kernel
+    # writes (tests/sentinel.py): a fresh torch.empty would be the block the
+    # previous iteration freed, with the right frame already in it
+    def f4():
+        return sentinel.target(torch, (H, W, 4), torch.float32)
+
+    def w8(rows=H):
+        return sentinel.target(torch, (rows, W), torch.int32)
+
     for _ in range(3):
-        assert torch.equal(R.render(W, H), ref_f)
-        assert torch.equal(R.render_rgba8(W, H), ref8)
-    band = R.render_band_rgba8(W, H, 8, 3, 1)
+        a = R.render(W, H, out=f4())
+        sentinel.assert_frame(a, ref_f)
+        assert torch.equal(a, ref_f)
+        a = R.render_rgba8(W, H, out=w8())
+        sentinel.assert_frame(a, ref8)
+        assert torch.equal(a, ref8)
+    band = R.render_band_rgba8(W, H, 8, 3, 1, out=w8(rm.shard_rows(H, 8, 3, 1)))
+    sentinel.assert_frame(band, ref8[[y for y in range(H) if (y // 8) % 3 == 1]])
     for _ in range(2):
-        assert torch.equal(R.render_band_rgba8(W, H, 8, 3, 1), band)
+        a = R.render_band_rgba8(W, H, 8, 3, 1, out=w8(band.shape[0]))
+        sentinel.assert_frame(a, band)
+        assert torch.equal(a, band)
     R.set_params(count_evals=1)
-    a, sa = R.render(W, H, stats=True)
-    b, sb = R.render(W, H, stats=True)
+    a, sa = R.render(W, H, out=f4(), stats=True)
+    b, sb = R.render(W, H, out=f4(), stats=True)
+    sentinel.assert_frame(a, ref_f)
+    sentinel.assert_frame(b, ref_f)
     assert torch.equal(a, ref_f) and torch.equal(b, ref_f) and sa["evals"] == sb["evals"]
     # an explicit order takes precedence; a wrong size is ignored
     tx, ty = R.tile_grid(W, H)
     R.set_tile_order(np.arange(tx * ty, dtype=np.uint32)[::-1].copy())
-    assert torch.equal(R.render(W, H), ref_f)
+    a = R.render(W, H, out=f4())
+    sentinel.assert_frame(a, ref_f)
+    assert torch.equal(a, ref_f)
     assert torch.equal(R.render(W + 8, H)[:, :W], R.render(W + 8, H)[:, :W])
     with pytest.raises(rm.RmError):
         R.set_tile_order(np.zeros(tx * ty, np.uint32))  # not a permutation
@@ -847,9 +868,12 @@ def test_latency_tiles_keep_pixels(R, torch_cuda):
     ref, st = R.render_rgba8(W, H, stats=True)
     R.set_params(count_evals=0, schedule=1)
     for _ in range(4):
-        assert torch.equal(R.render_rgba8(W, H), ref)
+        a = R.render_rgba8(W, H, out=sentinel.target(torch, (H, W), torch.int32))
+        sentinel.assert_frame(a, ref)
+        assert torch.equal(a, ref)
     R.set_params(count_evals=1)
-    a, sa = R.render_rgba8(W, H, stats=True)
+    a, sa = R.render_rgba8(W, H, out=sentinel.target(torch, (H, W), torch.int32), stats=True)
+    sentinel.assert_frame(a, ref)
     assert torch.equal(a, ref) and sa["evals"] == st["evals"]
     R.set_params(count_evals=0)
 
@@ -864,17 +888,27 @@ def test_persistent_waves_equal_hardware_dispatch(R, torch_cuda, scene):
     setup(R, scene, POSES["P1"], 128)
     R.set_params(count_evals=0, kernel="tile8")
     W, H = 200, 136
-    ref = R.render_rgba8(W, H)
-    band = R.render_band_rgba8(W, H, 8, 3, 1)
+    # (the references too may be ordered launches, the context's schedule being what the tests before left:
+    # into sentinel targets, no word of which may remain)
+    ref = R.render_rgba8(W, H, out=sentinel.target(torch, (H, W), torch.int32))
+    band = R.render_band_rgba8(W, H, 8, 3, 1, out=sentinel.target(torch, (rm.shard_rows(H, 8, 3, 1), W), torch.int32))
+    assert int((ref == sentinel.RGBA8_WORD).sum()) == 0
+    sentinel.assert_frame(band, ref[[y for y in range(H) if (y // 8) % 3 == 1]], "the reference row part")
     R.set_params(kernel="persist")
     s2 = torch.cuda.Stream()
     for i in range(8):
+        # (targets filled on the default stream and complete before the launch
+        # on s2: torch.full is ordered there, and synchronize() waits for it)
+        ta, tb = sentinel.target(torch, (H, W), torch.int32), sentinel.target(torch, tuple(band.shape), torch.int32)
+        torch.cuda.synchronize()
         if i % 2:
             R.set_stream(s2)
-        a = R.render_rgba8(W, H)
-        b = R.render_band_rgba8(W, H, 8, 3, 1)
+        a = R.render_rgba8(W, H, out=ta)
+        b = R.render_band_rgba8(W, H, 8, 3, 1, out=tb)
         R.set_stream(None)
         torch.cuda.synchronize()
+        sentinel.assert_frame(a, ref, f"launch {i}")
+        sentinel.assert_frame(b, band, f"launch {i}, the row part")
         assert torch.equal(a, ref), i
         assert torch.equal(b, band), i
     R.set_params(kernel="auto")

@@ -33,6 +33,7 @@ import raymarching_amd as rm
 from raymarching_amd import POSES, S0_POSE
 from tests import far_sky_ref as fs
 from tests import near_sky_ref as ref
+from tests import sentinel
 
 pytestmark = pytest.mark.gpu
 
@@ -154,7 +155,8 @@ def test_instrumented_frames_and_counts(R, golden, pose_name):
 
 @pytest.mark.parametrize("kernel", KERNELS)
 @pytest.mark.parametrize("pose_name", list(ref.POSE_SET))
-def test_timed_frame_equals_instrumented_frame_and_parent(R, golden, pose_name, kernel):
+def test_timed_frame_equals_instrumented_frame_and_parent(R, torch_cuda, golden, pose_name, kernel):
+    torch = torch_cuda
     for name in [n for n, c in CASES.items() if c[0] == pose_name]:
         what = f"{name} {kernel}"
         ref4, ref8, _, _ = render_instrumented(R, name, kernel)
@@ -168,11 +170,15 @@ def test_timed_frame_equals_instrumented_frame_and_parent(R, golden, pose_name, 
         o8 = bits(R.render_rgba8(W, H))
         assert np.array_equal(o8, ref8) and sha(o8) == want8, f"{what}: timed RGBA8 (row-major) differs"
         R.set_params(schedule=1)
+        # (every launch into a target no launch has written, tests/sentinel.py: a tile the order never dispatched
+        # shows instead of keeping the previous launch's pixels)
         for i in range(2):  # (the second launch of a geometry has an order and latency tiles)
-            o8, st8 = R.render_rgba8(W, H, stats=True)
+            o8, st8 = R.render_rgba8(W, H, out=sentinel.target(torch, (H, W), torch.int32), stats=True)
+            sentinel.assert_frame(o8, ref8, f"{what}: timed RGBA8 (schedule 1, launch {i})")
             assert sha(bits(o8)) == want8, f"{what}: timed RGBA8 (schedule 1, launch {i}) differs"
         for i in range(2):
-            f, st4 = R.render(W, H, stats=True)
+            f, st4 = R.render(W, H, out=sentinel.target(torch, (H, W, 4), torch.float32), stats=True)
+            sentinel.assert_frame(f, ref4, f"{what}: timed float4 (schedule 1, launch {i})")
             assert sha(bits(f)) == want4, f"{what}: timed float4 (schedule 1, launch {i}) differs"
         if kernel != "tile16":  # (the four-wave workgroups have no tile order)
             assert st8["dispatch"] == "adaptive" and st8["lat_tiles"] > 0, st8

@@ -18,6 +18,7 @@ import pytest
 import raymarching_amd as rm
 from tests import lib_edges as edges
 from tests import lib_ref64 as ref64
+from tests import sentinel
 from tests.golden import lib_kat_cases as kat
 from tests.parity import assert_parity
 
@@ -483,5 +484,7 @@ def test_plugin_adaptive_dispatch_order_keeps_pixels(R, torch_cuda):
     R.set_params(max_steps=128, count_evals=0, schedule=0)
     ref = R.render_rgba8(160, 96)
     R.set_params(schedule=1)
-    for _ in range(3):
-        assert torch.equal(R.render_rgba8(160, 96), ref)
+    for _ in range(3):  # (into a target no launch has written: tests/sentinel.py)
+        a = R.render_rgba8(160, 96, out=sentinel.target(torch, (96, 160), torch.int32))
+        sentinel.assert_frame(a, ref)
+        assert torch.equal(a, ref)

@@ -27,6 +27,7 @@ import pytest
 
 import raymarching_amd as rm
 from raymarching_amd import POSES, S0_POSE
+from tests import sentinel
 
 pytestmark = pytest.mark.gpu
 
@@ -115,7 +116,8 @@ def test_instrumented_frames_equal_the_parent(R, golden, name):
 
 @pytest.mark.parametrize("kernel", KERNELS)
 @pytest.mark.parametrize("name", list(CASES))
-def test_timed_frames_equal_the_parent(R, golden, name, kernel):
+def test_timed_frames_equal_the_parent(R, torch_cuda, golden, name, kernel):
+    torch = torch_cuda
     f4, w8 = golden[f"{name}.f4"], golden[f"{name}.rgba8"]
     what = f"{name} {kernel}"
     W, H = setup_case(R, name, 0, kernel, schedule=0)
@@ -124,11 +126,15 @@ def test_timed_frames_equal_the_parent(R, golden, name, kernel):
     assert np.array_equal(bits(f), f4), f"{what}: timed float4 (row-major) differs"
     assert np.array_equal(bits(R.render_rgba8(W, H)), w8), f"{what}: timed RGBA8 (row-major) differs"
     R.set_params(schedule=1)
+    # (every ordered launch into a target no launch has written, tests/sentinel.py: a tile the order never
+    # dispatched shows instead of keeping the previous launch's pixels)
     for _ in range(3):  # (an order exists from the second launch of a geometry on)
-        o8, st8 = R.render_rgba8(W, H, stats=True)
+        o8, st8 = R.render_rgba8(W, H, out=sentinel.target(torch, (H, W), torch.int32), stats=True)
+    sentinel.assert_frame(o8, w8, f"{what}: timed RGBA8 (adaptive)")
     assert np.array_equal(bits(o8), w8), f"{what}: timed RGBA8 (adaptive) differs"
     for _ in range(2):
-        f, st4 = R.render(W, H, stats=True)
+        f, st4 = R.render(W, H, out=sentinel.target(torch, (H, W, 4), torch.float32), stats=True)
+    sentinel.assert_frame(f, f4, f"{what}: timed float4 (adaptive)")
     assert np.array_equal(bits(f), f4), f"{what}: timed float4 (adaptive) differs"
     if kernel != "tile16":  # (the four-wave workgroups have no tile order)
         assert st8["dispatch"] == "adaptive" and st4["dispatch"] == "adaptive", (st8, st4)
@@ -158,7 +164,9 @@ def test_bands_equal_the_parents_rows(R, golden, name, band, nshards):
                 assert np.array_equal(bits(part), w8[rows[4:]]), f"{what}: RGBA8 rows from packed row 4"
             R.set_params(schedule=1)
             for _ in range(3):
-                b, st = R.render_band_rgba8(W, H, band, nshards, shard, stats=True)
+                b, st = R.render_band_rgba8(W, H, band, nshards, shard, stats=True,
+                                            out=sentinel.target(torch, (len(rows), W), torch.int32))
+            sentinel.assert_frame(b, w8[rows], f"{what}: RGBA8 (adaptive)")
             assert np.array_equal(bits(b), w8[rows]), f"{what}: RGBA8 (adaptive)"
             assert kernel == "tile16" or st["dispatch"] == "adaptive", st
             # the instrumented kernels take the same rows

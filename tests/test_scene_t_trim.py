@@ -22,6 +22,7 @@ import pytest
 import oracle
 import raymarching_amd as rm
 from raymarching_amd import POSES, S0_POSE
+from tests import sentinel
 
 pytestmark = pytest.mark.gpu
 
@@ -88,7 +89,8 @@ def test_instrumented_frames_equal_the_parent(R, golden, name):
 
 
 @pytest.mark.parametrize("name", list(CASES))
-def test_timed_frames_equal_the_parent(R, golden, name):
+def test_timed_frames_equal_the_parent(R, torch_cuda, golden, name):
+    torch = torch_cuda
     f4, w8 = golden[f"{name}.f4"], golden[f"{name}.rgba8"]
     W, H = setup_case(R, name, 0, schedule=0)
     f, st = R.render(W, H, stats=True)
@@ -98,17 +100,22 @@ def test_timed_frames_equal_the_parent(R, golden, name):
     rows = band_rows(H)
     assert np.array_equal(bits(R.render_band_rgba8(W, H, *BAND)), w8[rows]), f"{name}: RGBA8 band (row-major) differs"
     R.set_params(schedule=1)
+    # (every ordered launch into a target no launch has written, tests/sentinel.py: a tile the order never
+    # dispatched shows instead of keeping the previous launch's pixels)
     for _ in range(3):  # (an order exists from the second launch of a geometry on)
-        o8, st = R.render_rgba8(W, H, stats=True)
+        o8, st = R.render_rgba8(W, H, out=sentinel.target(torch, (H, W), torch.int32), stats=True)
     assert st["dispatch"] == "adaptive", st
+    sentinel.assert_frame(o8, w8, f"{name}: timed RGBA8 (adaptive)")
     assert np.array_equal(bits(o8), w8), f"{name}: timed RGBA8 (adaptive) differs"
     for _ in range(2):
-        f, st = R.render(W, H, stats=True)
+        f, st = R.render(W, H, out=sentinel.target(torch, (H, W, 4), torch.float32), stats=True)
     assert st["dispatch"] == "adaptive", st
+    sentinel.assert_frame(f, f4, f"{name}: timed float4 (adaptive)")
     assert np.array_equal(bits(f), f4), f"{name}: timed float4 (adaptive) differs"
     for _ in range(2):
-        b, st = R.render_band_rgba8(W, H, *BAND, stats=True)
+        b, st = R.render_band_rgba8(W, H, *BAND, out=sentinel.target(torch, (len(rows), W), torch.int32), stats=True)
     assert st["dispatch"] == "adaptive", st
+    sentinel.assert_frame(b, w8[rows], f"{name}: RGBA8 band (adaptive)")
     assert np.array_equal(bits(b), w8[rows]), f"{name}: RGBA8 band (adaptive) differs"
     R.set_params(schedule=0)
 
