@@ -27,8 +27,8 @@
 // sub-pixel offset), all rendered at --w x --h by one launch on one GPU.  With
 // --ppm NAME it writes NAME.0000.ppm, NAME.0001.ppm, ...; with --stats the JSON
 // line carries the launch's kernel_ms.  With --aa K[:threshold] the batch is
-// rendered antialiased (rm::Shader::renderBatchAA -> rm_render_batch_aa_rgba8,
-// every view's offset (0, 0)): the JSON line gains "aa": K and "refined": the
+// rendered antialiased (rm::Shader::renderBatchAAEx -> rm_render_batch_aa_ex_rgba8,
+// any scene again, every view's offset (0, 0)): the JSON line gains "aa": K and "refined": the
 // pixels refined over all views, and kernel_ms sums the batch, detect + plan
 // and refine launches.  With --post [--post-sample ..] [--tonemap ..] the batch
 // (antialiased or not) is rendered into a device target and the post passes run
@@ -45,9 +45,8 @@
 // (rm::RenderTexture::drawAAEx -> rm_render_aa_ex_rgba8: any scene, a .hip
 // scene plugin included): K = 2, 4 or 8 samples at
 // the pixels whose 3x3 neighbourhood spreads a colour channel by at least
-// threshold (0..255, default 32; 0: every pixel).  One GPU, the RGBA8 target
-// (with --views: built-in scenes); --stats then counts the base frame's, the detect and the
-// refine kernel.
+// threshold (0..255, default 32; 0: every pixel).  One GPU, the RGBA8 target;
+// --stats then counts the base frame's, the detect and the refine kernel.
 // --uniform sets a uniform the scene declares itself (a scene plugin's
 // `uniform vec4 u_ball = ...;`, rm.h rm_load_scene) once the scene is loaded:
 // one to four numbers for a float / vec2 / vec3 / vec4, one for an int or a
@@ -319,8 +318,8 @@ int main(int argc, char** argv) {
         }
         uint32_t* target = dev ? dev : px.data();
         const auto b0 = std::chrono::steady_clock::now();
-        if (aa_samples ? !shader.renderBatchAA(w, h, views.data(), n, target, aa_samples, aa_threshold, nullptr,
-                                               nullptr, &aa_st)
+        if (aa_samples ? !shader.renderBatchAAEx(w, h, views.data(), n, nullptr, 0, target, aa_samples, aa_threshold,
+                                                 nullptr, nullptr, &aa_st)
                        : !shader.renderBatchEx(w, h, views.data(), n, nullptr, 0, target, stats ? &st : nullptr)) {
             std::fprintf(stderr, "--views failed: %s\n", shader.lastError().c_str());
             return 1;

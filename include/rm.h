@@ -501,9 +501,10 @@ rm_status rm_render_accumulate_rgba8(rm_ctx *ctx, int W, int H, uint32_t *accum,
  * then RM_ERR_SCENE for a plugin built with RM_PLUGIN_EVAL_ONLY; mixed
  * pointers; then RM_ERR_SCENE if the refine kernel fails to compile, its log in
  * rm_last_error.  In every case the frame is untouched.
- *   Out of scope: supersampling of a plugin batch, float targets,
+ *   Out of scope: float targets,
  * RM_AA_LAYOUT=pixel for plugins, count_evals of the refine, banded / sharded /
- * wire renders. */
+ * wire renders.  (Supersampling of a plugin batch: rm_render_batch_aa_ex_rgba8
+ * below.) */
 typedef struct rm_aa_params {
     int32_t samples;   /* K: 2, 4 or 8 */
     int32_t threshold; /* 0..255       */
@@ -619,9 +620,10 @@ rm_status rm_render_batch_rgba8(rm_ctx *ctx, int W, int H, const rm_view *views,
  * (rm_last_error names the declared type), count < 1, count > 1 for a
  * non-array, count above the declared length (all RM_ERR_INVALID_ARGUMENT).
  * n = 0: RM_OK, nothing launched.
- *   Out of scope: supersampling of a plugin batch; per-view max_steps or
+ *   Out of scope: per-view max_steps or
  * resolution; device-resident view or uniform arrays; count_evals and step maps
- * per view; a dispatch order across views; multi-GPU batches. */
+ * per view; a dispatch order across views; multi-GPU batches.  (Supersampling
+ * of a plugin batch: rm_render_batch_aa_ex_rgba8 below.) */
 typedef struct rm_view_uniform {
     const char *name;    /* a uniform the loaded scene declares                        */
     int32_t components;  /* 1..4, the declared type's (int, bool: 1)                   */
@@ -678,14 +680,74 @@ rm_status rm_compile_scene_batch(const char *file_name, char *log, size_t log_si
  * exclusive prefix of the views' group counts, the groups' total, the counts'
  * total) rounded up to a line, and a queue word per pixel; `bytes` may be NULL.
  * The view records are the view batch's own scratch.
- *   Out of scope: scene plugins, float targets, a threshold or sample count per
+ *   Out of scope: float targets, a threshold or sample count per
  * view, views of different sizes, multi-GPU batches and count_evals of the
- * refine. */
+ * refine.  (Scene plugins: the _ex calls below.)
+ *
+ * rm_refine_batch_ex_rgba8 and rm_render_batch_aa_ex_rgba8 take any scene, a
+ * scene plugin included, with the scene's own uniforms set per view (DESIGN.md
+ * 2.32).  View v's frame, mask part and refined[v] are, byte for byte, what
+ * rm_render_aa_ex_rgba8 gives, with the same rm_aa_params, after u_pos, u_mouse
+ * and u_time are set to the view's values and each uniform of the list is set to
+ * view v's values by the matching rm_set_uniform* call (the list is
+ * rm_render_batch_ex's); every unlisted uniform has the context's value at the
+ * call.  rm_refine_batch_ex_rgba8 relates to rm_refine_ex_rgba8 the same way.
+ * The context's pose, seed and uniform values are neither read nor changed: the
+ * getters answer after the call what they answered before.  Pointer kinds, the
+ * staging of host buffers, the stats fields, asynchrony, the size rule and
+ * rm_batch_aa_scratch_bytes are rm_render_batch_aa_rgba8's; batches in flight
+ * follow rm_render_batch_ex's rule.
+ *   For a built-in scene with n_uniforms == 0 the calls are
+ * rm_refine_batch_rgba8 / rm_render_batch_aa_rgba8, the same path and the same
+ * bytes; with n_uniforms > 0 they return RM_ERR_INVALID_ARGUMENT.
+ * (rm_refine_batch_rgba8 and rm_render_batch_aa_rgba8 themselves keep refusing a
+ * scene plugin.)
+ *   A plugin's batch refine kernel is a fourth code object of the scene (detect
+ * and plan are compiled in), compiled on the first of these calls after the
+ * scene was loaded and cached by its text, as the batch and AA forms are; a call
+ * that must compile blocks for that long.  rm_batch_aa_prepare compiles and
+ * loads what rm_render_batch_aa_ex_rgba8 needs, the batch form and this one, now:
+ * RM_OK at once for a built-in scene or when both are loaded, RM_ERR_NO_SCENE
+ * without a scene, RM_ERR_SCENE for a plugin built with RM_PLUGIN_EVAL_ONLY.
+ * rm_compile_scene_batch_aa is rm_compile_scene for the new code object (no GPU
+ * needed; a built-in scene: RM_OK with the compiled-in log; an
+ * RM_PLUGIN_EVAL_ONLY scene: RM_ERR_SCENE).
+ *   The refine runs G one-wave workgroups per view (DESIGN.md 2.32 has the rule
+ * for G); the environment variable RM_PLUGIN_BATCH_AA_COLUMNS=<G>, read at every
+ * call, overrides it for measurements.  Any G gives the same bytes.
+ *   Errors, all checked before any pointer is used or anything is written, in
+ * this order:
+ *    1. the size rule above broken (RM_ERR_INVALID_ARGUMENT);
+ *    2. a NULL params, or a NULL views or frames with n > 0;
+ *    3. samples not 2, 4 or 8, or a threshold outside 0..255;
+ *    4. a view whose offset is not exactly (0, 0);
+ *    5. n_uniforms < 0, or a NULL `uniforms` with n_uniforms > 0;
+ *    6. no scene (RM_ERR_NO_SCENE);
+ *    7. a plugin built with RM_PLUGIN_EVAL_ONLY (RM_ERR_SCENE);
+ *    8. a built-in scene with n_uniforms > 0 (RM_ERR_INVALID_ARGUMENT);
+ *    9. per entry of the list, rm_render_batch_ex's faults, the message in
+ *       rm_last_error (RM_ERR_INVALID_ARGUMENT);
+ *   10. n = 0: RM_OK, stats zeroed, nothing launched;
+ *   11. mixed host and device pointers (RM_ERR_INVALID_ARGUMENT);
+ *   12. RM_ERR_SCENE, with the log in rm_last_error, if a form of the plugin
+ *       fails to compile.
+ *   Out of scope: float targets, a threshold or sample count per view, views of
+ * different sizes, device-resident view or uniform arrays, count_evals of the
+ * refine, RM_AA_LAYOUT=pixel, an order of the base frames' tiles across views
+ * and multi-GPU batches. */
 rm_status rm_batch_aa_scratch_bytes(int W, int H, int n, int64_t *bytes);
 rm_status rm_refine_batch_rgba8(rm_ctx *ctx, int W, int H, const rm_view *views, int n, const rm_aa_params *params,
                                 uint32_t *frames, uint8_t *mask, uint32_t *refined, rm_aa_stats *stats);
 rm_status rm_render_batch_aa_rgba8(rm_ctx *ctx, int W, int H, const rm_view *views, int n, const rm_aa_params *params,
                                    uint32_t *out, uint8_t *mask, uint32_t *refined, rm_aa_stats *stats);
+rm_status rm_refine_batch_ex_rgba8(rm_ctx *ctx, int W, int H, const rm_view *views, int n,
+                                   const rm_view_uniform *uniforms, int n_uniforms, const rm_aa_params *params,
+                                   uint32_t *frames, uint8_t *mask, uint32_t *refined, rm_aa_stats *stats);
+rm_status rm_render_batch_aa_ex_rgba8(rm_ctx *ctx, int W, int H, const rm_view *views, int n,
+                                      const rm_view_uniform *uniforms, int n_uniforms, const rm_aa_params *params,
+                                      uint32_t *out, uint8_t *mask, uint32_t *refined, rm_aa_stats *stats);
+rm_status rm_batch_aa_prepare(rm_ctx *ctx);
+rm_status rm_compile_scene_batch_aa(const char *file_name, char *log, size_t log_size);
 
 /* rm_render_band / rm_render_rows into RGBA8 rows (W uint32 per row). */
 rm_status rm_render_band_rgba8(rm_ctx *ctx, int W, int H, int band, int nshards, int shard, uint32_t *out,

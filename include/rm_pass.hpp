@@ -174,6 +174,21 @@ public:
         const rm_aa_params p{samples, threshold};
         return ctx_ && rm_render_batch_aa_rgba8(ctx_, w, h, views, n, &p, out, mask, refined, stats) == RM_OK;
     }
+    // rm.h rm_render_batch_aa_ex_rgba8: renderBatchAA for any scene, a scene
+    // plugin included, with uniforms the scene declares set per view as
+    // renderBatchEx sets them -- view v's frame is what setUniform(pose) +
+    // setUniform of view v's values + RenderTexture::drawAAEx gives.  A plugin's
+    // batch and batch-refine kernels are compiled on the first call after
+    // loadFromFile unless prepareBatchAA did it before.  With a built-in scene:
+    // renderBatchAA, and a non-empty list fails.
+    bool renderBatchAAEx(int w, int h, const rm_view* views, int n, const rm_view_uniform* uniforms, int nUniforms,
+                         std::uint32_t* out, int samples = 4, int threshold = 32, std::uint8_t* mask = nullptr,
+                         std::uint32_t* refined = nullptr, rm_aa_stats* stats = nullptr) {
+        const rm_aa_params p{samples, threshold};
+        return ctx_ && rm_render_batch_aa_ex_rgba8(ctx_, w, h, views, n, uniforms, nUniforms, &p, out, mask, refined,
+                                                   stats) == RM_OK;
+    }
+    bool prepareBatchAA() { return ctx_ && rm_batch_aa_prepare(ctx_) == RM_OK; }
 
 private:
     bool setArray(const char* name, int components, const float* v, std::size_t length) {

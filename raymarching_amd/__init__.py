@@ -11,6 +11,7 @@ from ._lib import EXPORTS, LIB_PATH, POST_SAMPLES, TONEMAPS, RmError, lib  # noq
 from .api import (Comm, Renderer, RenderTexture, Shader, ShaderLoader, aa_edge_mask, aa_offsets,  # noqa: F401
                   batch_aa_scratch_bytes, post_batch_plan,
                   comm_get_id, compile_scene, compile_scene_aa, compile_scene_batch, cycle_rows, pack_views, shard_rows, sharded_layout, wire_capacity, render_code_hash, wire_workspace_bytes)
+from . import batch_aa_ex  # noqa: F401  (the _ex forms of render_batch_aa: functions of a module of their own)
 from .cameras import cubemap_rays, equirect_rays, fisheye_rays, turntable  # noqa: F401
 from .poses import POSES, S0_POSE  # noqa: F401
 

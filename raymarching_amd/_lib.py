@@ -218,6 +218,12 @@ SIGNATURES = {
                                c.POINTER(RmAaStats)], c.c_int),
     "rm_render_batch_aa_rgba8": ([vp, c.c_int, c.c_int, vp, c.c_int, c.POINTER(RmAaParams), vp, vp, vp,
                                   c.POINTER(RmAaStats)], c.c_int),
+    "rm_refine_batch_ex_rgba8": ([vp, c.c_int, c.c_int, vp, c.c_int, vp, c.c_int, c.POINTER(RmAaParams), vp, vp, vp,
+                                  c.POINTER(RmAaStats)], c.c_int),
+    "rm_render_batch_aa_ex_rgba8": ([vp, c.c_int, c.c_int, vp, c.c_int, vp, c.c_int, c.POINTER(RmAaParams), vp, vp, vp,
+                                     c.POINTER(RmAaStats)], c.c_int),
+    "rm_batch_aa_prepare": ([vp], c.c_int),
+    "rm_compile_scene_batch_aa": ([cp, vp, c.c_size_t], c.c_int),
     "rm_post_batch_plan": ([c.c_int, c.c_int, c.c_int, c.c_int64, c.POINTER(RmPostBatchPlan)], c.c_int),
     "rm_set_post_batch_scratch_limit": ([vp, c.c_int64], c.c_int),
     "rm_post_frag_batch": ([vp, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, vp, vp], c.c_int),

@@ -645,9 +645,17 @@ class Renderer:
         (batch_prepare compiles it ahead).  For a built-in scene: render_batch,
         and a non-empty `uniforms` raises.  views, out, rgba8, stats: as
         render_batch."""
-        import numpy as np
         v = pack_views(views)
         n = len(v)
+        arr, n_entries, _keep = self._view_uniforms("render_batch_ex", uniforms, n)
+        return self._render("rm_render_batch_ex", rgba8, (n, H, W), out, stats, int(W), int(H), self._ptr(v), n, arr,
+                            n_entries)
+
+    def _view_uniforms(self, what, uniforms, n):
+        """The rm_view_uniform list of a `uniforms` dict (render_batch_ex's) for n
+        views -> (pointer to the list or None, entries, what must stay alive
+        until the call returns: the list and the arrays it points into)."""
+        import numpy as np
         infos = {u.name.decode(): u for u in self._uniform_infos()}
         entries, keep = [], []
         for name, values in (uniforms or {}).items():
@@ -662,14 +670,13 @@ class Renderer:
             elif a.ndim == 2:
                 a = a.reshape(a.shape[0], 1, a.shape[1])
             if a.ndim != 3 or a.shape[0] != n:
-                raise ValueError(f"render_batch_ex: uniform {name!r} needs [n], [n, components] or "
+                raise ValueError(f"{what}: uniform {name!r} needs [n], [n, components] or "
                                  f"[n, count, components] values for n = {n} views")
             keep.append((name.encode(), a))
             entries.append(_lib.RmViewUniform(keep[-1][0], int(a.shape[2]), int(a.shape[1]),
                                               ctypes.c_void_p(a.ctypes.data)))
         arr = (_lib.RmViewUniform * max(1, len(entries)))(*entries)
-        return self._render("rm_render_batch_ex", rgba8, (n, H, W), out, stats, int(W), int(H), self._ptr(v), n,
-                            ctypes.cast(arr, ctypes.c_void_p) if entries else None, len(entries))
+        return (ctypes.cast(arr, ctypes.c_void_p) if entries else None), len(entries), (arr, keep)
 
     def batch_prepare(self) -> None:
         """rm_batch_prepare: compile and load the loaded plugin's batch kernel

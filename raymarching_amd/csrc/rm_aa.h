@@ -18,7 +18,8 @@
 // A scene plugin's refine kernel (rm_plugin_kernels.h rm_plugin_aa_refine, the
 // AA form of the plugin's translation unit) is compiled by
 // hiprtc from this header's device part: aa_sample, aa_pack, aa_inv and
-// aa_refine_lane_sample.  Under __HIPCC_RTC__ everything else -- the standard
+// aa_refine_lane_sample, and the batch forms' batch_aa_refine_group.  Under
+// __HIPCC_RTC__ everything else -- the standard
 // headers, the launchers, the detect kernel and the lane = pixel layout -- is
 // left out.
 #pragma once
@@ -30,6 +31,7 @@
 #endif
 
 #include "rm_aa_rule.h"
+#include "rm_batch_aa_plan.h"
 #include "rm_render_direct.h"
 
 namespace rm {
@@ -170,6 +172,45 @@ __device__ __forceinline__ void aa_refine_lane_sample(const FrameConst& F, int k
         }
         if (active && sample == 0) frame[pix] = aa_pack<SC>(v3(sx, sy, sz));
     }
+}
+
+// One refine group of a view batch (rm_batch_aa.h; a scene plugin's batch-AA
+// form, rm_plugin_kernels.h rm_plugin_batch_aa_refine): entries gl * ppw .. of a
+// view's queue segment, lane = (entry, sample).  aa_refine_lane_sample's loop
+// body with the view's constants, count, queue and frame.
+template <int SC>
+__device__ __forceinline__ void batch_aa_refine_group(const FrameConst& G, int kshift, uint32_t count, uint32_t gl,
+                                                      const uint32_t* __restrict__ queue,
+                                                      uint32_t* __restrict__ frame, float ox, float oy) {
+    const int lane = threadIdx.x & 63;
+    const int K = 1 << kshift;
+    const uint32_t e = gl * rmbaa::group_entries(kshift) + (uint32_t)(lane >> kshift);
+    const bool active = e < count;
+    uint32_t pix = 0;
+    V3 c = v3s(0.0f);
+    if (active) {
+        pix = queue[e];
+        const int y = (int)(pix / (uint32_t)G.W), x = (int)(pix - (uint32_t)y * (uint32_t)G.W);
+        c = aa_sample<SC>(G, x, y, ox, oy);
+    }
+    float sx = c.x, sy = c.y, sz = c.z;
+    {
+#pragma clang fp contract(off)
+#pragma unroll
+        for (int o = 1; o < rmaa::kMaxSamples; o <<= 1) {
+            if (o < K) {  // (wave-uniform)
+                const float tx = __shfl_xor(sx, o, 64), ty = __shfl_xor(sy, o, 64), tz = __shfl_xor(sz, o, 64);
+                sx = sx + tx;
+                sy = sy + ty;
+                sz = sz + tz;
+            }
+        }
+        const float inv = aa_inv(kshift);
+        sx = sx * inv;
+        sy = sy * inv;
+        sz = sz * inv;
+    }
+    if (active && (lane & (K - 1)) == 0) frame[pix] = aa_pack<SC>(v3(sx, sy, sz));
 }
 
 #ifndef __HIPCC_RTC__

@@ -50,43 +50,7 @@ hipError_t launch_batch_aa_refine_o(int scene, const FrameConst& F, const void* 
 
 #ifdef RM_BATCH_AA_KERNELS  // the kernels' translation units (they define RM_AA_KERNELS too)
 
-// One refine group: entries gl * ppw .. of a view's queue segment, lane =
-// (entry, sample).  aa_refine_lane_sample's loop body (rm_aa.h) with the view's
-// constants, count, queue and frame.
-template <int SC>
-__device__ __forceinline__ void batch_aa_refine_group(const FrameConst& G, int kshift, uint32_t count, uint32_t gl,
-                                                      const uint32_t* __restrict__ queue,
-                                                      uint32_t* __restrict__ frame, float ox, float oy) {
-    const int lane = threadIdx.x & 63;
-    const int K = 1 << kshift;
-    const uint32_t e = gl * rmbaa::group_entries(kshift) + (uint32_t)(lane >> kshift);
-    const bool active = e < count;
-    uint32_t pix = 0;
-    V3 c = v3s(0.0f);
-    if (active) {
-        pix = queue[e];
-        const int y = (int)(pix / (uint32_t)G.W), x = (int)(pix - (uint32_t)y * (uint32_t)G.W);
-        c = aa_sample<SC>(G, x, y, ox, oy);
-    }
-    float sx = c.x, sy = c.y, sz = c.z;
-    {
-#pragma clang fp contract(off)
-#pragma unroll
-        for (int o = 1; o < rmaa::kMaxSamples; o <<= 1) {
-            if (o < K) {  // (wave-uniform)
-                const float tx = __shfl_xor(sx, o, 64), ty = __shfl_xor(sy, o, 64), tz = __shfl_xor(sz, o, 64);
-                sx = sx + tx;
-                sy = sy + ty;
-                sz = sz + tz;
-            }
-        }
-        const float inv = aa_inv(kshift);
-        sx = sx * inv;
-        sy = sy * inv;
-        sz = sz * inv;
-    }
-    if (active && (lane & (K - 1)) == 0) frame[pix] = aa_pack<SC>(v3(sx, sy, sz));
-}
+// (one refine group, batch_aa_refine_group: rm_aa.h's device part, which a scene plugin's batch-AA form shares)
 
 // Scenes S0 / T: the launch's FrameConst with the view's short record put in,
 // as rm_batch.h's rm_render_batch does.  The record's address is wave-uniform

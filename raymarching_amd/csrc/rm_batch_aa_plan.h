@@ -18,7 +18,9 @@
 //                                  v, prefix[n] the total; then the sum of the counts
 //   queue     n * W * H            view v's entries (y * W + x) from v * W * H
 #pragma once
+#ifndef __HIPCC_RTC__  // (a scene plugin's batch-AA form takes group_entries through rm_aa.h)
 #include <cstdint>
+#endif
 
 #if defined(__HIPCC__)
 #define RM_BAA_HD __host__ __device__

@@ -677,7 +677,8 @@ rm_status rm_scene_eval_form(rm_ctx *ctx, const float *points, int64_t n, int fo
     return scene_eval_form(ctx, points, n, form, dist, material, aux, "rm_scene_eval_form");
 }
 
-// rm_compile_scene; form: the batch or the AA form of the code object (rm_compile_scene_batch, rm_compile_scene_aa)
+// rm_compile_scene; form: the batch, the AA or the batch-AA form of the code object (rm_compile_scene_batch,
+// rm_compile_scene_aa, rm_compile_scene_batch_aa)
 static rm_status compile_scene(const char *file_name, char *log, size_t log_size, rmplugin::Form form) {
     if (!file_name) return RM_ERR_INVALID_ARGUMENT;
     std::string src, err, clog;
@@ -710,6 +711,10 @@ rm_status rm_compile_scene_batch(const char *file_name, char *log, size_t log_si
 
 rm_status rm_compile_scene_aa(const char *file_name, char *log, size_t log_size) {
     return compile_scene(file_name, log, log_size, rmplugin::FORM_AA);
+}
+
+rm_status rm_compile_scene_batch_aa(const char *file_name, char *log, size_t log_size) {
+    return compile_scene(file_name, log, log_size, rmplugin::FORM_BATCH_AA);
 }
 
 int rm_abi_version(void) { return RM_ABI_VERSION; }

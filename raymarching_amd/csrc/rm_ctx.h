@@ -285,6 +285,17 @@ rm_status batch_ex_blocks(rm_ctx *ctx, const BatchEx &ex, int n, std::vector<uin
 // the loaded plugin's batch kernel, compiled and loaded if it is not yet
 rm_status batch_ex_ready(rm_ctx *ctx);
 
+// the loaded plugin's batch refine kernel (the batch-AA form), compiled and loaded if it is not yet
+rm_status batch_aa_ex_ready(rm_ctx *ctx);
+
+// ---- rm_batch_aa_host.cpp
+// rm_refine_batch_rgba8 / rm_render_batch_aa_rgba8 (ex null: a scene plugin is refused) and their _ex forms: the
+// checks in include/rm.h's order, the staging of host buffers, the records, the batch launch when `render`, then
+// count memset, detect, plan and the scene's refine; `what` names the call in the messages
+rm_status batch_aa_run(rm_ctx *ctx, const char *what, int W, int H, const rm_view *views, int n, const rm_aa_params *p,
+                       uint32_t *frames, uint8_t *mask, uint32_t *refined, rm_aa_stats *stats, bool render,
+                       const BatchEx *ex);
+
 // ---- rm_aa_host.cpp
 // the stats tail of a refine and of a batch's (rm_batch_aa_host.cpp): aa_ev2 recorded and waited for, the device
 // word at `count` into stats->refined, detect_ms = ev0..ev1 and refine_ms = ev1..aa_ev2

@@ -45,6 +45,9 @@ namespace glsl {
 // first argument plus blockIdx.z * kRecordStride, wave-uniform.  The memory is
 // read-only for the launch and is read through the constant address space too,
 // so the loads stay scalar and invariant, and hoist as the frame form's do.
+// The batch-AA form (#define RM_PLUGIN_BATCH_AA; rm_render_batch_aa_ex_rgba8,
+// DESIGN.md 2.32) reads the same records the same way: its refine workgroups
+// have their view in blockIdx.z too.
 typedef const __attribute__((address_space(4))) FrameConst* KernargFrame;
 typedef const __attribute__((address_space(4))) char* KernargBytes;
 constexpr int kUniformOffset = (int)((sizeof(FrameConst) + 15) & ~(size_t)15);
@@ -55,7 +58,7 @@ constexpr int kRecordStride = kUniformOffset;
 #endif
 // where the pass's uniforms and the scene's block are read from
 __device__ __forceinline__ KernargBytes plugin_bytes() {
-#ifdef RM_PLUGIN_BATCH
+#if defined(RM_PLUGIN_BATCH) || defined(RM_PLUGIN_BATCH_AA)
     // (the kernel's first parameter, a pointer to the records)
     typedef const __attribute__((address_space(4))) KernargBytes* KernargPointer;
     const KernargBytes records = *(KernargPointer)__builtin_amdgcn_kernarg_segment_ptr();

@@ -1,5 +1,7 @@
 // rm_plugin_batch_host.cpp -- rm_render_batch_ex, rm_render_batch_ex_rgba8 and
-// rm_batch_prepare (include/rm.h):
+// rm_batch_prepare (include/rm.h), and the supersampled forms
+// rm_refine_batch_ex_rgba8, rm_render_batch_aa_ex_rgba8 and rm_batch_aa_prepare
+// (through rm_batch_aa_host.cpp's batch_aa_run):
 // view batches of any scene, a scene plugin's with its uniforms set per view.
 // The call itself is rm_batch_host.cpp's batch_run -- the checks, the pinned
 // blocks, the records' scratch buffer, the staging and the one launch are
@@ -38,6 +40,15 @@ rm_status batch_ex_ready(rm_ctx *ctx) {
     return fail(ctx, RM_ERR_SCENE, "scene plugin \"" + ctx->plugin.file + "\": the batch form failed to compile:\n" + err);
 }
 
+rm_status batch_aa_ex_ready(rm_ctx *ctx) {
+    std::string err;
+    hipError_t e = hipSuccess;
+    if (rmplugin::batch_aa_ready(ctx->plugin, err, e)) return RM_OK;
+    if (e != hipSuccess) return hip_fail(ctx, e, "scene plugin batch-AA module load");
+    return fail(ctx, RM_ERR_SCENE,
+                "scene plugin \"" + ctx->plugin.file + "\": the batch-AA form failed to compile:\n" + err);
+}
+
 }  // namespace rmhost
 
 extern "C" {
@@ -62,6 +73,28 @@ rm_status rm_batch_prepare(rm_ctx *ctx) {
     if (ctx->scene != rm::SCENE_PLUGIN) return RM_OK;  // (compiled in)
     RM_HIP(hipSetDevice(ctx->device));
     return batch_ex_ready(ctx);
+}
+
+rm_status rm_refine_batch_ex_rgba8(rm_ctx *ctx, int W, int H, const rm_view *views, int n,
+                                   const rm_view_uniform *uniforms, int n_uniforms, const rm_aa_params *params,
+                                   uint32_t *frames, uint8_t *mask, uint32_t *refined, rm_aa_stats *stats) {
+    const BatchEx ex = {uniforms, n_uniforms};
+    return batch_aa_run(ctx, "rm_refine_batch_ex_rgba8", W, H, views, n, params, frames, mask, refined, stats, false,
+                        &ex);
+}
+
+rm_status rm_render_batch_aa_ex_rgba8(rm_ctx *ctx, int W, int H, const rm_view *views, int n,
+                                      const rm_view_uniform *uniforms, int n_uniforms, const rm_aa_params *params,
+                                      uint32_t *out, uint8_t *mask, uint32_t *refined, rm_aa_stats *stats) {
+    const BatchEx ex = {uniforms, n_uniforms};
+    return batch_aa_run(ctx, "rm_render_batch_aa_ex_rgba8", W, H, views, n, params, out, mask, refined, stats, true,
+                        &ex);
+}
+
+rm_status rm_batch_aa_prepare(rm_ctx *ctx) {
+    if (rm_status st = rm_batch_prepare(ctx)) return st;  // (its checks, and the batch form)
+    if (ctx->scene != rm::SCENE_PLUGIN) return RM_OK;     // (compiled in)
+    return batch_aa_ex_ready(ctx);
 }
 
 }  // extern "C"

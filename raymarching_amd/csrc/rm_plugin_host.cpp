@@ -12,6 +12,8 @@
 // an unchanged scene costs no compilation.
 #include "rm_plugin_host.h"
 
+#include "rm_plugin_batch_aa_grid.h"
+
 #include <hip/hiprtc.h>
 
 #include <cstdio>
@@ -224,6 +226,8 @@ std::string translation_unit(const std::string& src, const std::string& file, co
     if (form == FORM_BATCH) head = "#define RM_PLUGIN_BATCH 1\n" + head;
     // (the AA form likewise, so that a refined sample rounds as the frame kernel's pixel does)
     if (form == FORM_AA) head = "#define RM_PLUGIN_AA 1\n" + head;
+    // (and the batch-AA form: the AA form's samples from the batch form's records)
+    if (form == FORM_BATCH_AA) head = "#define RM_PLUGIN_BATCH_AA 1\n" + head;
     return head + "#include \"rm_plugin.h\"\n" + defines +
            instance("namespace rm {\nnamespace glsl {\n", "}  // namespace glsl\n}  // namespace rm\n", "", "") +
            instance("namespace rm {\nnamespace glsl {\nnamespace probe {\n",
@@ -240,11 +244,12 @@ bool compile(const std::string& src, const std::string& file, Code& code, std::s
     if (!rmuniform::parse(src, file, uniforms, scene, log)) return false;
     const std::string tu = translation_unit(scene, file, uniforms, form);
     log.clear();
-    // debugging: the TU and its code object (a cached one too), the batch and AA forms' beside the frame form's
+    // debugging: the TU and its code object (a cached one too), the other forms' beside the frame form's
     auto dump = [&](const Code& c) {
         const char* dir = std::getenv("RM_PLUGIN_DUMP");
         if (!dir) return;
-        const std::string stem = std::string(dir) + (form == FORM_BATCH ? "/plugin_batch" : form == FORM_AA ? "/plugin_aa" : "/plugin");
+        const std::string stem = std::string(dir) + (form == FORM_BATCH ? "/plugin_batch" : form == FORM_AA ? "/plugin_aa" :
+                                                        form == FORM_BATCH_AA ? "/plugin_batch_aa" : "/plugin");
         std::ofstream(stem + "_tu.hip") << tu;
         std::ofstream(stem + ".co", std::ios::binary).write(c->data(), (std::streamsize)c->size());
     };
@@ -319,12 +324,13 @@ hipError_t load(const Code& code, int uniform_slots, Module& m) {
     }
     n.code = code;
     n.uniform_slots = uniform_slots;
-    unload(m);  // (the batch and AA forms of the scene before with it)
+    unload(m);  // (the batch, AA and batch-AA forms of the scene before with it)
     m = n;
     return hipSuccess;
 }
 
 void unload(Module& m) {
+    if (m.batch_aa_mod) (void)hipModuleUnload(m.batch_aa_mod);
     if (m.aa_mod) (void)hipModuleUnload(m.aa_mod);
     if (m.batch_mod) (void)hipModuleUnload(m.batch_mod);
     if (m.mod) (void)hipModuleUnload(m.mod);
@@ -376,24 +382,55 @@ bool batch_ready(Module& m, std::string& err, hipError_t& e) {
            form_ready(m, FORM_BATCH, "batch", "rm_plugin_render_batch", m.batch_mod, m.render_batch, err, e);
 }
 
+namespace {
+
+// the one-wave workgroups of `fn` the device holds at once (rm_aa.h's launch_aa_refine_as counts them so)
+hipError_t device_waves(hipFunction_t fn, unsigned& waves) {
+    int dev = 0, cus = 0, per_cu = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e == hipSuccess) e = hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, 0);
+    if (e == hipSuccess) waves = (unsigned)std::max(1, cus * std::max(per_cu, 1));
+    return e;
+}
+
+// form_ready, then the device's waves of the form's kernel into `waves`; a failure leaves the form unloaded
+bool refine_form_ready(Module& m, Form form, const char* label, const char* kernel, hipModule_t& mod,
+                       hipFunction_t& fn, unsigned& waves, std::string& err, hipError_t& e) {
+    if (!form_ready(m, form, label, kernel, mod, fn, err, e)) return false;
+    e = device_waves(fn, waves);
+    if (e == hipSuccess) return true;
+    (void)hipModuleUnload(mod);
+    mod = nullptr;
+    fn = nullptr;
+    err = load_error(label, e);
+    return false;
+}
+
+}  // namespace
+
 bool aa_ready(Module& m, std::string& err, hipError_t& e) {
     e = hipSuccess;
-    if (m.aa_refine) return true;
-    if (!form_ready(m, FORM_AA, "AA", "rm_plugin_aa_refine", m.aa_mod, m.aa_refine, err, e)) return false;
     // the grid, as rm_aa.h's launch_aa_refine_as fixes it: the one-wave workgroups the device holds at once
-    int dev = 0, cus = 0, per_cu = 0;
-    e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e == hipSuccess) e = hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, m.aa_refine, 64, 0);
-    if (e != hipSuccess) {
-        (void)hipModuleUnload(m.aa_mod);
-        m.aa_mod = nullptr;
-        m.aa_refine = nullptr;
-        err = load_error("AA", e);
-        return false;
-    }
-    m.aa_grid = (unsigned)std::max(1, cus * std::max(per_cu, 1));
-    return true;
+    return m.aa_refine ||
+           refine_form_ready(m, FORM_AA, "AA", "rm_plugin_aa_refine", m.aa_mod, m.aa_refine, m.aa_grid, err, e);
+}
+
+bool batch_aa_ready(Module& m, std::string& err, hipError_t& e) {
+    e = hipSuccess;
+    return m.batch_aa_refine || refine_form_ready(m, FORM_BATCH_AA, "batch-AA", "rm_plugin_batch_aa_refine",
+                                                  m.batch_aa_mod, m.batch_aa_refine, m.batch_aa_waves, err, e);
+}
+
+hipError_t launch_batch_aa_refine(const Module& m, const void* records, int W, int H, int n, int kshift,
+                                  const uint32_t* counters, uint32_t cstride, const uint32_t* queue, uint32_t* frames,
+                                  hipStream_t s) {
+    if (!m.batch_aa_refine) return hipErrorInvalidDeviceFunction;
+    if (n <= 0) return hipSuccess;
+    const uint32_t g = rmpbaa::columns_override(std::getenv("RM_PLUGIN_BATCH_AA_COLUMNS"),
+                                                rmpbaa::columns(W, H, n, kshift, m.batch_aa_waves));
+    return launch(m.batch_aa_refine, dim3(g, 1, (unsigned)n), 64, m, nullptr, nullptr, s,
+                  {&records, &kshift, &counters, &cstride, &queue, &frames});
 }
 
 hipError_t launch_aa_refine(const Module& m, const rm::FrameConst& F, const uint32_t* uniforms, int kshift,

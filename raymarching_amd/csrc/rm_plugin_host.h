@@ -35,9 +35,10 @@ std::string glsl_source(const std::string& src);
 // unit, the frame form's text behind one #define at its head -- the same scene
 // text and options: FORM_BATCH (rm_plugin.h RM_PLUGIN_BATCH), whose kernel is
 // rm_plugin_render_batch, and FORM_AA (RM_PLUGIN_AA), whose kernel is
-// rm_plugin_aa_refine.  A scene that defines RM_PLUGIN_EVAL_ONLY has neither and
-// fails to compile.
-enum Form : int { FORM_FRAME = 0, FORM_BATCH = 1, FORM_AA = 2 };
+// rm_plugin_aa_refine, and FORM_BATCH_AA (RM_PLUGIN_BATCH_AA), whose kernel is
+// rm_plugin_batch_aa_refine.  A scene that defines RM_PLUGIN_EVAL_ONLY has none
+// of them and fails to compile.
+enum Form : int { FORM_FRAME = 0, FORM_BATCH = 1, FORM_AA = 2, FORM_BATCH_AA = 3 };
 bool compile(const std::string& src, const std::string& file, Code& code, std::string& log,
              rmuniform::Table& uniforms, Form form = FORM_FRAME);
 
@@ -61,6 +62,11 @@ struct Module {
     hipModule_t aa_mod = nullptr;
     hipFunction_t aa_refine = nullptr;
     unsigned aa_grid = 0;
+    // the batch-AA form (rm_refine_batch_ex_rgba8): as the AA form, by batch_aa_ready; `batch_aa_waves`, the one-wave
+    // workgroups of its kernel the device holds at once, is what rm_plugin_batch_aa_grid.h's rule starts from
+    hipModule_t batch_aa_mod = nullptr;
+    hipFunction_t batch_aa_refine = nullptr;
+    unsigned batch_aa_waves = 0;
 };
 // on the current device; m keeps its old module on failure
 hipError_t load(const Code& code, int uniform_slots, Module& m);
@@ -75,6 +81,15 @@ bool aa_ready(Module& m, std::string& err, hipError_t& e);
 // hipErrorInvalidDeviceFunction before aa_ready
 hipError_t launch_aa_refine(const Module& m, const rm::FrameConst& F, const uint32_t* uniforms, int kshift,
                             const uint32_t* count, const uint32_t* queue, uint32_t* frame, hipStream_t s);
+// The batch-AA form likewise (rm_plugin_batch_aa_refine and the device's waves of it).
+bool batch_aa_ready(Module& m, std::string& err, hipError_t& e);
+// The refine of a batch's n views of W x H for m's scene, on dim3(G, 1, n) one-wave workgroups with G from
+// rm_plugin_batch_aa_grid.h (RM_PLUGIN_BATCH_AA_COLUMNS, read here at every call, overrides it): `records` as
+// launch_render_batch's; view v's count at counters[v * cstride], its queue segment and its frame at v * W * H
+// words of `queue` and `frames` (rm_batch_aa_plan.h); hipErrorInvalidDeviceFunction before batch_aa_ready
+hipError_t launch_batch_aa_refine(const Module& m, const void* records, int W, int H, int n, int kshift,
+                                  const uint32_t* counters, uint32_t cstride, const uint32_t* queue, uint32_t* frames,
+                                  hipStream_t s);
 // bytes of one view's record: the FrameConst, then the uniform block at rm_plugin.h's kUniformOffset
 constexpr size_t kBatchUniformOffset = (sizeof(rm::FrameConst) + 15) & ~(size_t)15;
 static_assert(kBatchUniformOffset == 592, "include/rm.h states a plugin record's bytes");

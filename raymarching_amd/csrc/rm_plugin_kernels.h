@@ -8,7 +8,7 @@
 #pragma once
 #include "rm_rays.h"
 #include "rm_shade.h"
-#ifdef RM_PLUGIN_AA
+#if defined(RM_PLUGIN_AA) || defined(RM_PLUGIN_BATCH_AA)
 #include "rm_aa.h"
 #endif
 
@@ -107,6 +107,31 @@ extern "C" __global__ __launch_bounds__(64) void rm_plugin_aa_refine(rm::FrameCo
     RM_UNIFORM_PRELOAD();
     rm::aa_refine_lane_sample<rm::SCENE_PLUGIN>(F, kshift, count, queue, frame);
 }
+#elif defined(RM_PLUGIN_BATCH_AA)
+// The batch-AA form of the translation unit (include/rm.h rm_refine_batch_ex_rgba8) has this
+// kernel alone: the refine of every view of a batch.  A scene's functions find their view's record from the
+// workgroup's index alone (rm_plugin.h plugin_bytes), so a workgroup serves one view, blockIdx.z, as in the batch
+// form: gridDim.x one-wave workgroups per view stride over the groups of that view's queue segment, each group
+// rm_aa.h's batch_aa_refine_group, the body of the compiled-in batch kernels.  No workgroup waits for another; the
+// workgroups of a view that queued nothing leave after one scalar load.  `records` is the first parameter, where
+// plugin_bytes reads it; the uniforms are loaded at the top as rm_plugin_render_batch loads them.
+extern "C" __global__ __launch_bounds__(64) void rm_plugin_batch_aa_refine(const void* records, int kshift,
+                                                                           const uint32_t* counters, uint32_t cstride,
+                                                                           const uint32_t* queue, uint32_t* frames) {
+    const uint32_t count = counters[(size_t)blockIdx.z * cstride];
+    const uint32_t ppw = rmbaa::group_entries(kshift);
+    if ((uint32_t)blockIdx.x * ppw >= count) return;  // (wave-uniform: before any record is read)
+    const rm::glsl::KernargFrame K = rm::glsl::plugin_frame();
+    asm volatile("" ::"s"(K->time), "s"(K->pos_x), "s"(K->pos_y), "s"(K->pos_z), "s"(K->mouse_x), "s"(K->mouse_y),
+                 "s"(K->res_x), "s"(K->res_y));
+    RM_UNIFORM_PRELOAD();
+    const rm::FrameConst& G = *(const rm::FrameConst*)K;
+    const size_t px = (size_t)G.W * (size_t)G.H * (size_t)blockIdx.z;
+    float ox, oy;
+    rmaa::sample_offset(1 << kshift, (int)(threadIdx.x & 63u) & ((1 << kshift) - 1), ox, oy);
+    for (uint32_t gl = blockIdx.x; gl * ppw < count; gl += gridDim.x)  // (count < 2^30: no wrap)
+        rm::batch_aa_refine_group<rm::SCENE_PLUGIN>(G, kshift, count, gl, queue + px, frames + px, ox, oy);
+}
 #else
 extern "C" __global__ __launch_bounds__(64) void rm_plugin_render(rm::FrameConst F, RM_UNIFORM_PARAM void* out,
                                                                   int rgba8, unsigned long long* evals) {
@@ -126,14 +151,16 @@ extern "C" __global__ __launch_bounds__(64) void rm_plugin_shade(rm::FrameConst 
     RM_UNIFORM_PRELOAD();
     rm::shade_rays_one<rm::SCENE_PLUGIN, rm::SHADE_PER_LAUNCH, rm::SHADE_PER_LAUNCH>(F, Q);
 }
-#endif  // RM_PLUGIN_BATCH, RM_PLUGIN_AA
+#endif  // RM_PLUGIN_BATCH, RM_PLUGIN_AA, RM_PLUGIN_BATCH_AA
 #elif defined(RM_PLUGIN_BATCH)
 #error "the scene defines RM_PLUGIN_EVAL_ONLY (no render kernel): it has no batch form"
 #elif defined(RM_PLUGIN_AA)
 #error "the scene defines RM_PLUGIN_EVAL_ONLY (no render kernel): it has no AA form"
+#elif defined(RM_PLUGIN_BATCH_AA)
+#error "the scene defines RM_PLUGIN_EVAL_ONLY (no render kernel): it has no batch-AA form"
 #endif
 
-#if !defined(RM_PLUGIN_BATCH) && !defined(RM_PLUGIN_AA)
+#if !defined(RM_PLUGIN_BATCH) && !defined(RM_PLUGIN_AA) && !defined(RM_PLUGIN_BATCH_AA)
 // sceneSDF(p) at explicit points (rm_scene_eval)
 extern "C" __global__ __launch_bounds__(256) void rm_plugin_eval(rm::FrameConst F, RM_UNIFORM_PARAM const float* pts,
                                                                  long long n, float* dist, float* mat) {
